@@ -71,6 +71,10 @@ def parse():
     ap.add_argument('--no-concurrent', action='store_true', help='skip the extras that run next to the headline')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the extra_c5_forward / extra_c2 child runs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (image, depth, alpha, radii and, when '
+                         'training, the gradients the caller receives) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, '
+                         'seeded sample of each array that does not fit), plus DIR/manifest.json; rank 0 only')
     return ap.parse_args()
 
 
@@ -105,17 +109,23 @@ def main():
     args = parse()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as typed: become the torch.distributed.run launch of N ranks (one per GPU, RCCL over
-        # xGMI; EXA_BENCH_BACKEND=gloo lets several ranks share one GPU for the smoke test of this very path)
-        n_dev = torch.cuda.device_count()
-        if n_dev < args.gpus and os.environ.get('EXA_BENCH_BACKEND', 'nccl') == 'nccl':
-            print('bench.py: --gpus %d but only %d device(s) visible (RCCL needs one GPU per rank)' % (args.gpus, n_dev),
-                  file=sys.stderr)
-            sys.exit(2)
+        # xGMI; EXA_BENCH_BACKEND=gloo lets several ranks share one GPU for the smoke test of this very path).  This process
+        # never opens the GPU itself: the device count comes from a short-lived child, the ranks run in child processes.
+        import subprocess
+        if os.environ.get('EXA_BENCH_BACKEND', 'nccl') == 'nccl':
+            r = subprocess.run([sys.executable, '-c', 'import torch; print(torch.cuda.device_count())'],
+                               capture_output=True, text=True, timeout=120)
+            n_dev = int(r.stdout.split()[-1]) if r.returncode == 0 and r.stdout.split() else 0
+            if n_dev < args.gpus:
+                print('bench.py: --gpus %d but only %d device(s) visible (RCCL needs one GPU per rank)' % (args.gpus, n_dev),
+                      file=sys.stderr)
+                sys.exit(2)
         port = os.environ.get('MASTER_PORT') or str(29500 + os.getpid() % 2000)
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
                '--master-addr', '127.0.0.1', '--master-port', port, os.path.abspath(__file__)] + sys.argv[1:]
-        os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-        os.execv(sys.executable, cmd)
+        env = dict(os.environ)
+        env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
+        sys.exit(subprocess.run(cmd, env=env).returncode)
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -329,21 +339,29 @@ def main():
     probe = torch.zeros(P, 3, device=device, requires_grad=train)
     surf_in = params + [probe]
     kw_col = dict(shs=params[4]) if use_sh else dict(colors_precomp=params[4])
+    # --dump-outputs with the surface as the timed path: DETACHED outputs of the latest step (a live `out` would keep this
+    # step's autograd graph, and with it the parameters' AccumulateGrad nodes, alive into whatever runs next)
+    last_surface = {'on': bool(args.dump_outputs) and launch == 'surface'}
 
     def step_surface(i, reduce=True):
         k = i & 1
         if reduce:
             reducer_wait(k)
         if train:
-            color = rasts[i % n_my](means3D=params[0], means2D=probe, opacities=params[3], scales=params[1], rotations=params[2],
-                                    **kw_col)[0]
-            grads = torch.autograd.grad([color], surf_in, grad_outputs=[dL_dimg])
+            out = rasts[i % n_my](means3D=params[0], means2D=probe, opacities=params[3], scales=params[1], rotations=params[2],
+                                  **kw_col)
+            grads = torch.autograd.grad([out[0]], surf_in, grad_outputs=[dL_dimg])
             if reduce and reducer is not None:
                 reducer.pack(grads[:5], k)
                 reducer.reduce(k)
+            if last_surface['on']:
+                last_surface['out'], last_surface['grads'] = tuple(t.detach() for t in out), grads
         else:
             with torch.no_grad():
-                rasts[i % n_my](means3D=params[0], means2D=probe, opacities=params[3], scales=params[1], rotations=params[2], **kw_col)
+                out = rasts[i % n_my](means3D=params[0], means2D=probe, opacities=params[3], scales=params[1], rotations=params[2],
+                                      **kw_col)
+            if last_surface['on']:
+                last_surface['out'] = out
 
     step = step_surface if launch == 'surface' else step_abi_group if S > 1 else step_abi
     units = S if (launch == 'abi' and S > 1) else 1          # views per step
@@ -351,6 +369,25 @@ def main():
     def finish():
         if reducer is not None:
             reducer.finish()
+
+    def last_step_outputs(i):
+        """What timed step i handed its caller: the image, depth, alpha and radii of its (last) view and, when training, the
+        gradients -- for N > 1 the all-reduced ones, as the reducer's buffer holds them."""
+        grad_names = ('means3D', 'scales', 'rotations', 'opacities', 'shs' if use_sh else 'colors_precomp')
+        if launch == 'abi':
+            o = sr.outputs(slot=S - 1)
+            arrays = {k: o[k] for k in ('color', 'depth', 'alpha', 'radii')}
+            if train:
+                g = sr.grad_outputs((i & 1) if (reducer is not None or S > 1) else 0)
+                arrays.update(('grad_' + k, g[k]) for k in grad_names + ('means2D',))
+            return arrays
+        arrays = dict(zip(('color', 'radii', 'depth', 'alpha'), last_surface['out'][:4]))
+        if train:
+            grads = list(last_surface['grads'])
+            if reducer is not None:
+                grads[:5] = reducer.buffer_views(i & 1)
+            arrays.update(('grad_' + k, grads[j]) for j, k in enumerate(grad_names + ('means2D',)))
+        return arrays
 
     def timed(fn, n, w, settle_n=0):
         """settle_n + w untimed steps, then n steps between synchronisations; seconds."""
@@ -377,6 +414,14 @@ def main():
     settle = int(os.environ.get('EXA_BENCH_SETTLE_STEPS', '300'))
     wait_host[0] = 0.0
     elapsed_local = timed(step, args.steps, args.warmup, settle)
+    if args.dump_outputs and rank == 0:
+        i_last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, last_step_outputs(i_last),
+                     {'config': args.config, 'mode': mode, 'launch': launch, 'views_in_flight': S, 'n_gpus': world,
+                      'steps': args.steps, 'warmup': args.warmup, 'last_step': i_last,
+                      'ring_view': my_views[((i_last * S + S - 1) if S > 1 else i_last) % n_my]})
+    last_surface.clear()
+    last_surface['on'] = False
     if world > 1:
         dist.barrier()
     # (the clock of the contract: barrier + synchronize on both sides of exactly K steps -- `timed` synchronises before it
@@ -610,6 +655,34 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this many bytes of .npy payload in all
+DUMP_SEED = 0             # the sample of an array that does not fit: randperm(numel, seed DUMP_SEED)[:cap], sorted
+
+
+def dump_outputs(out_dir, arrays, meta):
+    """Write ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` in float32, at most DUMP_BYTES in all: the largest arrays are
+    replaced by the same seeded sample of their flattened elements in every run, so two builds compare element for element.
+    ``out_dir/manifest.json`` records shapes, sample sizes and ``meta``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    host = {k: v.detach().to('cpu', torch.float32) for k, v in arrays.items()}
+    cap = max(t.numel() for t in host.values())
+    while sum(min(t.numel(), cap) for t in host.values()) * 4 > DUMP_BYTES:
+        cap //= 2
+    manifest = {'dtype': 'float32', 'max_bytes': DUMP_BYTES, 'sample_seed': DUMP_SEED, 'meta': meta, 'arrays': {}}
+    for k, t in host.items():
+        entry = {'shape': list(t.shape), 'source_dtype': str(arrays[k].dtype).replace('torch.', '')}
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:cap].sort().values
+            t = t.reshape(-1)[idx]
+            entry['sampled'] = cap
+        np.save(os.path.join(out_dir, k + '.npy'), t.numpy())
+        manifest['arrays'][k] = entry
+    with open(os.path.join(out_dir, 'manifest.json'), 'w') as f:
+        json.dump(manifest, f, indent=1)
 
 
 def surface_throughput(step_surface, args, exa):
