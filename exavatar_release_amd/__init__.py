@@ -4,6 +4,10 @@ Public surface (drop-in for ``diff_gaussian_rasterization_depth`` as used at ref
 ``avatar/common/nets/module.py:11,609-640``):
 
     from exavatar_release_amd import GaussianRasterizationSettings, GaussianRasterizer
+
+and for the face render (pytorch3d ``MeshRasterizer`` + ``TexturesUV`` at reference ``avatar/common/nets/layer.py:23-68``):
+
+    from exavatar_release_amd import MeshRenderer, get_face_index_map_xy
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -12,8 +16,9 @@ from .losses import SSIM, PhotometricLoss, RGBLoss
 from .renderer import ITERATION_RENDERS, GaussianRenderer, GraphedRenderer, render_iteration, render_many, render_views
 from .graphed import GraphedIteration
 from .static import StaticRender, required_capacity
+from .mesh import Fragments, MeshRenderer, get_face_index_map_xy
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
-           'SSIM', 'RGBLoss', 'PhotometricLoss']
+           'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments']

@@ -152,6 +152,36 @@ SIGNATURES = {
 }
 TIMING_SLOTS = 9
 
+
+# ---- the triangle rasterizer of the face render (include/exa_mesh.h): its own table, so SIGNATURES stays the ABI of
+# exa_raster.h alone
+class ExaMeshGeometry(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('verts', c_void_p), ('faces', c_void_p), ('focal', c_void_p), ('princpt', c_void_p)]
+
+
+class ExaMeshTexture(ctypes.Structure):
+    _fields_ = [('C', ctypes.c_int32), ('tex_H', ctypes.c_int32), ('tex_W', ctypes.c_int32), ('tex_N', ctypes.c_int32),
+                ('texture', c_void_p), ('face_uvs', c_void_p)]
+
+
+class ExaMeshWorkspaceSizes(ctypes.Structure):
+    _fields_ = [('face_bytes', ctypes.c_uint64), ('bin_bytes', ctypes.c_uint64), ('grad_bytes', ctypes.c_uint64)]
+
+
+_GP = ctypes.POINTER(ExaMeshGeometry)
+_TP = ctypes.POINTER(ExaMeshTexture)
+MESH_SIGNATURES = {
+    'exa_mesh_version': (ctypes.c_int, []),
+    'exa_mesh_last_error': (ctypes.c_char_p, []),
+    'exa_mesh_workspace_sizes': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ExaMeshWorkspaceSizes)]),
+    'exa_mesh_vertex_faces': (ctypes.c_int, [_I32, _I32, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_forward': (ctypes.c_int, [_GP, _TP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_backward': (ctypes.c_int, [_GP, _TP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -171,6 +201,10 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in MESH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
     if lib.exa_raster_version() < 139:
         raise RuntimeError('exavatar_release_amd: libexa_raster.so is too old')
     _lib = lib
@@ -181,6 +215,18 @@ def check(rc):
     if rc != 0:
         msg = load().exa_raster_last_error()
         raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_raster error', rc))
+
+
+def check_mesh(rc):
+    if rc != 0:
+        msg = load().exa_mesh_last_error()
+        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_mesh error', rc))
+
+
+def mesh_workspace_sizes(N, F, H, W):
+    out = ExaMeshWorkspaceSizes()
+    check_mesh(load().exa_mesh_workspace_sizes(N, F, H, W, ctypes.byref(out)))
+    return out
 
 
 def workspace_sizes(P, W, H, capacity):

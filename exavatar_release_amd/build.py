@@ -34,6 +34,8 @@ SOURCES = {
     'preprocess_bwd.hip': [],
     'ssim.hip': [],
     'api.hip': [],
+    # the face render's bilinear blend must round as F.grid_sample's does (the reference tests `mask == 1`)
+    'mesh_raster.hip': ['-ffp-contract=off'],
 }
 
 
@@ -56,8 +58,9 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    with open(os.path.join(HERE, '..', 'include', 'exa_raster.h'), 'rb') as f:
-        h.update(f.read())
+    for hdr in ('exa_raster.h', 'exa_mesh.h'):
+        with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
+            h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())
     return h.hexdigest()
 

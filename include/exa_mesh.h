@@ -1,0 +1,100 @@
+/*
+ * exa_mesh.h -- C ABI of the MI355X-native differentiable triangle rasterizer with a fused UV-texture sample.
+ *
+ * This is the native boundary under ExAvatar's face render: pytorch3d's `MeshRasterizer` + `TexturesUV` as the
+ * reference calls them in `get_face_index_map_xy` / `MeshRenderer` (avatar/common/nets/layer.py:23-68).  The Python
+ * drop-ins over it are `exavatar_release_amd.mesh.MeshRenderer` and `exavatar_release_amd.mesh.get_face_index_map_xy`;
+ * the conventions (projection, coverage, depth test, perspective-correct barycentrics, texture sampling) are written
+ * out in that module's docstring.  It lives in the same `libexa_raster.so` as include/exa_raster.h.
+ *
+ * Conventions (those of exa_raster.h)
+ *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
+ *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
+ *     state between calls.  Workspace sizes follow from the shapes alone (exa_mesh_workspace_sizes): there is no
+ *     capacity and no overflow path.
+ *   - fp32 geometry and texture, int32 topology, int64 `pix_to_face`; contiguous row-major arrays.
+ *   - N meshes of ONE topology per call (the packed layout): verts[N,V,3] in camera space (x right, y down, z forward;
+ *     the reference's world->camera transform stays with the caller), faces[F,3], focal[N,2], princpt[N,2].
+ *   - work is enqueued on `stream`; no call synchronises the device.
+ *   - return value: 0 = ok; < 0 = invalid argument (EXA_MESH_E_*); > 0 = HIP error code (hipError_t).
+ *   - the backward is atomic-free and bit-deterministic: the same inputs give the same bits on every call.
+ */
+#ifndef EXA_MESH_H
+#define EXA_MESH_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define EXA_MESH_VERSION 100            /* 0.1.0.0: first version */
+#define EXA_MESH_CELL 64                /* faces are binned to 64x64-pixel cells */
+#define EXA_MESH_TILE 16                /* the forward raster runs one workgroup per 16x16-pixel tile */
+#define EXA_MESH_MAX_CHANNELS 8         /* texture channels per call */
+
+#define EXA_MESH_E_INVALID (-1)
+#define EXA_MESH_E_NULLPTR (-2)
+
+/* One call's scene: N meshes of one topology seen by N pinhole cameras, rendered at H x W. */
+typedef struct ExaMeshGeometry {
+    int32_t N, V, F;                    /* meshes, vertices per mesh, faces */
+    int32_t H, W;                       /* image rows, columns */
+    const float* verts;                 /* [dev] [N, V, 3] camera-space positions */
+    const int32_t* faces;               /* [dev] [F, 3] vertex indices, each in [0, V) */
+    const float* focal;                 /* [dev] [N, 2] (fx, fy) in pixels */
+    const float* princpt;               /* [dev] [N, 2] (cx, cy) in pixels */
+} ExaMeshGeometry;
+
+/* The UV texture of a fused render (pytorch3d TexturesUV): `face_uvs` holds the three corner uvs of every face, already
+ * in pytorch3d's convention (v up); the map is sampled vertically flipped, bilinear, align_corners, border padding. */
+typedef struct ExaMeshTexture {
+    int32_t C;                          /* channels, 1 .. EXA_MESH_MAX_CHANNELS */
+    int32_t tex_H, tex_W;               /* texture rows, columns (each >= 1) */
+    int32_t tex_N;                      /* 1 (one map for all meshes) or N */
+    const float* texture;               /* [dev] [tex_N, C, tex_H, tex_W] */
+    const float* face_uvs;              /* [dev] [F, 3, 2] */
+} ExaMeshTexture;
+
+typedef struct ExaMeshWorkspaceSizes {
+    uint64_t face_bytes;                /* per-face screen records: written by forward, read by backward */
+    uint64_t bin_bytes;                 /* per-cell face bitmasks: forward only */
+    uint64_t grad_bytes;                /* per-face corner gradients: backward only */
+} ExaMeshWorkspaceSizes;
+
+int exa_mesh_version(void);
+/* Message of the most recent failing call of this thread ("" if none). */
+const char* exa_mesh_last_error(void);
+
+int exa_mesh_workspace_sizes(int32_t N, int32_t F, int32_t H, int32_t W, ExaMeshWorkspaceSizes* out);
+
+/* Host-side helper: the vertex -> (face, corner) lists the backward gathers over, in CSR form and in a fixed order
+ * (ascending face, then corner).  `faces` [F,3], `offsets` [V+1] and `entries` [3F] (value 3 * face + corner) are HOST
+ * memory.  Build once per topology and copy to the device. */
+int exa_mesh_vertex_faces(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* entries);
+
+/* Rasterize (and, with `tex` != NULL, texture) N meshes.
+ *   face_ws, bin_ws  [dev] workspaces of the sizes above; face_ws must stay untouched until the matching backward.
+ *   pix_to_face      [dev] [N, H, W] int64: n * F + f of the nearest covering face, -1 for background (required).
+ *   zbuf             [dev] [N, H, W] or NULL: interpolated view-space z, -1 for background.
+ *   bary             [dev] [N, H, W, 3] or NULL: perspective-correct barycentrics, -1 for background.
+ *   render           [dev] [N, C, H, W]: the sampled texture, -1 in every channel of a background pixel; required with
+ *                    `tex`, ignored without. */
+int exa_mesh_forward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, void* face_ws, void* bin_ws,
+                     int64_t* pix_to_face, float* zbuf, float* bary, float* render, void* stream);
+
+/* dL/dverts from the gradients of the forward's outputs.  `g`, `tex`, `face_ws` and `pix_to_face` are those of the
+ * forward.  Any of dL_dzbuf [N,H,W], dL_dbary [N,H,W,3] and dL_drender [N,C,H,W] may be NULL (no gradient);
+ * dL_drender needs `tex`.  vert_offsets / vert_entries: exa_mesh_vertex_faces' CSR, on the device.
+ *   grad_ws    [dev] workspace of grad_bytes.
+ *   dL_dverts  [dev] [N, V, 3], fully written (vertices no face uses get 0). */
+int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const void* face_ws,
+                      const int64_t* pix_to_face, const float* dL_dzbuf, const float* dL_dbary, const float* dL_drender,
+                      const int32_t* vert_offsets, const int32_t* vert_entries, void* grad_ws, float* dL_dverts,
+                      void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* EXA_MESH_H */
