@@ -48,8 +48,8 @@ __device__ __forceinline__ void stage_splat(BatchLds& s, int lane, const float2&
 // |trace| r^2, a definite form is >= lambda_min r^2 in magnitude, and lambda_min / lambda_max >= det / trace^2.  (ca, cb, cc) as
 // staged (scaled, NEGATIVE definite: [[ca, cb/2], [cb/2, cc]]); the all-zero record staged behind the end of a list counts as
 // safe (its sum is lop = -inf exactly).  Both blends vote once per staged batch; a group of four WITH an unsafe entry (needles
-// beyond ~600 : 1, broken covariances -- never an avatar or a scene splat) takes the guard as a fix-up behind the evaluation
-// (power_guard4), every other group evaluates without it: two compares and a scalar AND less per splat and pixel.
+// beyond ~600 : 1, broken covariances -- never an avatar or a scene splat) takes the guard on its unsafe entries as a fix-up
+// behind the evaluation (power_guard4), every other group evaluates without it: two compares and a scalar AND less per splat and pixel.
 __device__ __forceinline__ bool conic_safe(float ca, float cb, float cc) {
     const float tr = ca + cc;
     return ca <= 0.0f && cc <= 0.0f && 4.0f * ca * cc - cb * cb >= 1e-5f * (tr * tr);
@@ -109,15 +109,21 @@ __device__ __forceinline__ Alpha4 splat_alpha4(const Ops4& o, float fx, float fy
     r.took[2] = __builtin_amdgcn_ballot_w64(hi.vis0); r.took[3] = __builtin_amdgcn_ballot_w64(hi.vis1);
     return r;
 }
-// The guard of a group with an unsafe conic (conic_safe): power > 0 -> the splat is skipped at this pixel.
-__device__ __forceinline__ void power_guard4(Alpha4& e, const Ops4& o) {
+// The guard of the UNSAFE entries of a group (conic_safe; bit j of `unsafe4` = entry j, wave-uniform): power > 0 -> the splat
+// is skipped at this pixel.  Per entry, not per group: the forward groups the list, the backward the compacted list, so
+// the group of a safe splat differs between the passes; and a safe conic can still round p2 one ulp above lop (lop at a
+// binade boundary, e.g. opacity 0.5, a few 1e-4 px from a pixel centre: tests/test_gpu_decisions.py), which a group-wide
+// guard skipped -- in one pass and not the other.
+__device__ __forceinline__ void power_guard4(Alpha4& e, const Ops4& o, uint32_t unsafe4) {
     const float lop[4] = {o.op.x, o.op.y, o.op.z, o.op.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const bool neg = e.p2[j] <= lop[j];
-        e.alpha[j] = neg ? e.alpha[j] : 0.0f;
-        e.Ag[j] = neg ? e.Ag[j] : 0.0f;
-        e.took[j] &= __builtin_amdgcn_ballot_w64(neg);
+        if ((unsafe4 >> j) & 1u) {
+            const bool neg = e.p2[j] <= lop[j];
+            e.alpha[j] = neg ? e.alpha[j] : 0.0f;
+            e.Ag[j] = neg ? e.Ag[j] : 0.0f;
+            e.took[j] &= __builtin_amdgcn_ballot_w64(neg);
+        }
     }
 }
 

@@ -375,7 +375,7 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
                 const bool live = T > 0.0f;
                 const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(live);
                 Alpha4 e = splat_alpha4(ops, fx, fy, live);
-                if ((unsafe >> k) & 0xfull) power_guard4(e, ops);
+                if ((unsafe >> k) & 0xfull) power_guard4(e, ops, (uint32_t)((unsafe >> k) & 0xfull));
                 grad4(e, live_mask, col, k);
             };
             // two groups per trip, ping-pong operand registers (next group's operands in flight, no register rotation)

@@ -710,7 +710,7 @@ __global__ __launch_bounds__(RBLOCK) void render_fwd_kernel(Batch<RenderFwdArgs>
         auto group4 = [&](const Ops4& ops, int k) -> bool {
             const float4 c0 = s_b.col[k], c1 = s_b.col[k + 1], c2 = s_b.col[k + 2], c3 = s_b.col[k + 3];
             Alpha4 e = splat_alpha4(ops, fx, fy, true);
-            if ((unsafe >> k) & 0xfull) power_guard4(e, ops);
+            if ((unsafe >> k) & 0xfull) power_guard4(e, ops, (uint32_t)((unsafe >> k) & 0xfull));
             return blend4(e, c0, c1, c2, c3, k);
         };
         Ops4 opsA = load_ops4(s_b, 0);

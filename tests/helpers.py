@@ -170,3 +170,41 @@ def fuzz_case(trial):
     G, Gd, Ga = torch.randn(3, H, W, generator=g), torch.randn(1, H, W, generator=g), torch.randn(1, H, W, generator=g)
     bg = torch.rand(3, generator=g)
     return a, H, W, cam, G, Gd, Ga, bg
+
+
+def extract_weights(render_rgb, P, perm=None):
+    """w [P, H, W] (float64): the blend weight the forward gave every (Gaussian, pixel) pair, read off the forward itself.
+    ``render_rgb(rgb)`` renders the scene with colours ``rgb`` [P, 3] and background 0 and returns its image [3, H, W].
+    Three Gaussians per render carry the one-hot colours (1, 0, 0), (0, 1, 0), (0, 0, 1), all others black: channel c of
+    that image is exactly the weight of the c-th of them (every other term is an exact 0).  ceil(P / 3) renders;
+    ``perm``: the order in which the Gaussians are grouped.  Colour enters no decision, so the grouping must not
+    matter, and a blended pair has w >= (1/255) 1e-4 > 0: ``keep = w > 0``."""
+    order = torch.arange(P) if perm is None else perm
+    w = None
+    for s in range(0, P, 3):
+        grp = order[s:s + 3]
+        rgb = torch.zeros(P, 3)
+        rgb[grp, torch.arange(grp.numel())] = 1.0
+        img = render_rgb(rgb).detach().cpu().double()
+        if w is None:
+            w = torch.zeros(P, img.shape[1], img.shape[2], dtype=torch.float64)
+        w[grp] = img[:grp.numel()]
+    return w
+
+
+def needle_scene():
+    """The scene of tests/test_gpu_edge_cases.py::test_needle_conics_keep_the_power_guard: needles of 350 .. 3 000 px (conics
+    that blend.h conic_safe calls unsafe) among 56 ordinary splats.  Returns (assets, H, W, cam, bg, G)."""
+    from exavatar_release_amd import scenes
+    H, W, f = 40, 56, 100.0
+    a = scenes.dist_a_random(60, H, W, seed=5, focal=f, z_range=(2.0, 4.0))
+    g = torch.Generator().manual_seed(77)
+    for i, s in enumerate((12.0, 30.0, 100.0, 40.0)):
+        a['scale'][i] = torch.tensor([s, 1e-4, 1e-4])
+        a['mean_3d'][i] = torch.tensor([0.1 * i - 0.2, 0.05 * i - 0.1, 3.0])
+        q = torch.randn(4, generator=g)
+        a['rotation'][i] = q / q.norm()
+        a['opacity'][i] = 0.6
+    cam, bg = scenes.neutral_camera(H, W, focal=f), torch.rand(3, generator=g)
+    G = torch.randn(3, H, W, generator=g)
+    return a, H, W, cam, bg, G

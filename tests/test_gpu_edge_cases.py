@@ -22,7 +22,7 @@ from exavatar_release_amd import scenes
 from oracle import c_oracle as co
 from oracle import raster_oracle as ro
 from tests.helpers import (IMG_TOL, assert_grads_close, assert_image_close, fuzz_case, gaussians_near_pixels, grad_stats,
-                           image_stats, record_stats, rotation_grad_scale)
+                           image_stats, needle_scene, record_stats, rotation_grad_scale)
 
 pytestmark = pytest.mark.gpu
 
@@ -607,17 +607,7 @@ def test_needle_conics_keep_the_power_guard(dev):
     low-pass floor) is the one kind of splat whose groups keep upstream's `power > 0 -> skip` compare, as a fix-up behind
     the evaluation; every other group runs without it.  Needles of 350 .. 3 000 px among ordinary splats, against the C
     oracle at the usual bar (measured: 1.3e-5)."""
-    H, W, f = 40, 56, 100.0
-    a = scenes.dist_a_random(60, H, W, seed=5, focal=f, z_range=(2.0, 4.0))
-    g = torch.Generator().manual_seed(77)
-    for i, s in enumerate((12.0, 30.0, 100.0, 40.0)):
-        a['scale'][i] = torch.tensor([s, 1e-4, 1e-4])
-        a['mean_3d'][i] = torch.tensor([0.1 * i - 0.2, 0.05 * i - 0.1, 3.0])
-        q = torch.randn(4, generator=g)
-        a['rotation'][i] = q / q.norm()
-        a['opacity'][i] = 0.6
-    cam, bg = scenes.neutral_camera(H, W, focal=f), torch.rand(3, generator=g)
-    G = torch.randn(3, H, W, generator=g)
+    a, H, W, cam, bg, G = needle_scene()
     ag = _to(a, dev)
     out = exa.GaussianRenderer()(ag, (H, W), {k: v.to(dev) for k, v in cam.items()}, bg.to(dev))
     (out['img'] * G.to(dev)).sum().backward()
