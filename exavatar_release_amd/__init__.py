@@ -8,6 +8,10 @@ Public surface (drop-in for ``diff_gaussian_rasterization_depth`` as used at ref
 and for the face render (pytorch3d ``MeshRasterizer`` + ``TexturesUV`` at reference ``avatar/common/nets/layer.py:23-68``):
 
     from exavatar_release_amd import MeshRenderer, get_face_index_map_xy
+
+and for the Phong-shaded mesh panel (pytorch3d ``SoftPhongShader`` in reference ``avatar/common/utils/vis.py:73-109``):
+
+    from exavatar_release_amd import render_mesh
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -16,9 +20,10 @@ from .losses import SSIM, PhotometricLoss, RGBLoss
 from .renderer import ITERATION_RENDERS, GaussianRenderer, GraphedRenderer, render_iteration, render_many, render_views
 from .graphed import GraphedIteration
 from .static import StaticRender, required_capacity
-from .mesh import Fragments, MeshRenderer, get_face_index_map_xy
+from .mesh import Fragments, MeshRenderer, get_face_index_map_xy, render_mesh, shade_mesh, vertex_normals
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
-           'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments']
+           'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
+           'vertex_normals', 'shade_mesh', 'render_mesh']

@@ -170,8 +170,17 @@ class ExaMeshWorkspaceSizes(ctypes.Structure):
     _fields_ = [('face_bytes', ctypes.c_uint64), ('bin_bytes', ctypes.c_uint64), ('grad_bytes', ctypes.c_uint64)]
 
 
+class ExaMeshShading(ctypes.Structure):
+    _fields_ = [('light_location', ctypes.c_float * 3), ('light_ambient', ctypes.c_float * 3),
+                ('light_diffuse', ctypes.c_float * 3), ('light_specular', ctypes.c_float * 3),
+                ('material_ambient', ctypes.c_float * 3), ('material_diffuse', ctypes.c_float * 3),
+                ('material_specular', ctypes.c_float * 3), ('shininess', ctypes.c_float),
+                ('background', ctypes.c_float * 3)]
+
+
 _GP = ctypes.POINTER(ExaMeshGeometry)
 _TP = ctypes.POINTER(ExaMeshTexture)
+_SHP = ctypes.POINTER(ExaMeshShading)
 MESH_SIGNATURES = {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -180,6 +189,9 @@ MESH_SIGNATURES = {
     'exa_mesh_forward': (ctypes.c_int, [_GP, _TP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_mesh_backward': (ctypes.c_int, [_GP, _TP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_vertex_normals': (ctypes.c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_forward_shaded': (ctypes.c_int, [_GP, _SHP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // Differentiable triangle rasterizer with a fused UV-texture sample (include/exa_mesh.h): the face render of ExAvatar
-// (pytorch3d MeshRasterizer + TexturesUV at reference layer.py:23-68).  The conventions are derived in the docstring of
+// (pytorch3d MeshRasterizer + TexturesUV at reference layer.py:23-68), and a Phong-shaded forward for the mesh panel of
+// the reference's render_mesh (vis.py:73-109).  The conventions are derived in the docstring of
 // exavatar_release_amd/mesh.py; this file implements them.
 //
 // Pipeline (wave = 64 lanes, every kernel a plain launch on the caller's stream, no atomics, no memsets):
@@ -10,7 +11,9 @@
 //                    array is cells x ceil(F/32) words per mesh -- a size the host knows, so no capacity, no overflow.
 //   mesh_raster_fwd  one workgroup per 16x16 tile: filters its cell's mask against the tile into LDS, then every pixel
 //                    walks the surviving faces in index order and keeps the nearest (strict <, so the lower index wins
-//                    a tie).  Writes pix_to_face, zbuf, bary and -- TEX -- samples the texture into the NCHW render.
+//                    a tie).  Writes pix_to_face, zbuf, bary and -- TEX -- samples the texture into the NCHW render,
+//                    or -- SHADE -- Phong-shades the nearest face into the NHWC image (no barycentrics written out).
+//   mesh_vertex_normals  one thread per (mesh, vertex): sums its corners' edge cross products in CSR order, normalises.
 //   mesh_bwd_faces   one wave per (mesh, face): walks the face's bbox, keeps the pixels whose pix_to_face is this face,
 //                    chains dL/d(bary, zbuf[, render]) to the three corners' camera-space xyz, sums per lane in pixel
 //                    order and across the wave by a fixed butterfly.  9 floats per face into grad_ws.
@@ -147,6 +150,11 @@ struct Params {
     const int32_t* offsets;
     const int32_t* entries;
     float* dverts;
+    // shaded forward
+    const float* normals;
+    float* normals_out;
+    float* image;
+    ExaMeshShading sh;
 };
 
 // ---- forward -------------------------------------------------------------------------------------------------------
@@ -219,7 +227,35 @@ __global__ void __launch_bounds__(BLOCK) mesh_bin(Params P) {
     P.bins[((size_t)n * P.cells + c) * P.words + w] = m;
 }
 
-template <bool TEX>
+// x / max(|x|, 1e-6): F.normalize's eps, as pytorch3d's lighting applies it
+__device__ __forceinline__ void normalize3(float v[3]) {
+    const float d = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), 1e-6f);
+    v[0] = v[0] / d;
+    v[1] = v[1] / d;
+    v[2] = v[2] / d;
+}
+
+// pytorch3d phong_shading at one pixel (include/exa_mesh.h, ExaMeshShading): pos / nrm are the interpolated position and
+// normal in the caller's camera frame
+__device__ __forceinline__ void phong(const ExaMeshShading& sh, const float pos[3], const float nrm[3], float out[3]) {
+    float n[3] = {nrm[0], nrm[1], nrm[2]};
+    float l[3] = {sh.light_location[0] - pos[0], sh.light_location[1] - pos[1], sh.light_location[2] - pos[2]};
+    float v[3] = {-pos[0], -pos[1], -pos[2]};
+    normalize3(n);
+    normalize3(l);
+    normalize3(v);
+    const float cosv = n[0] * l[0] + n[1] * l[1] + n[2] * l[2];
+    const float diff = fmaxf(cosv, 0.f);
+    float vr = 0.f;
+    for (int k = 0; k < 3; ++k) vr += v[k] * (-l[k] + 2.f * cosv * n[k]);
+    const float a = cosv > 0.f ? fmaxf(vr, 0.f) : 0.f;
+    const float spec = powf(a, sh.shininess);          // powf(0, 0) = 1, as torch.pow
+    for (int c = 0; c < 3; ++c)
+        out[c] = (sh.light_ambient[c] * sh.material_ambient[c] + sh.material_diffuse[c] * (sh.light_diffuse[c] * diff)) +
+                 sh.material_specular[c] * (sh.light_specular[c] * spec);
+}
+
+template <bool TEX, bool SHADE = false>
 __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
     __shared__ uint32_t s_mask[BLOCK];
     __shared__ uint64_t s_nz[BLOCK / 64];
@@ -287,7 +323,7 @@ __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
         screen_bary(r, px - (float)r.bx0, py - (float)r.by0, qb.b);
         perspective(r, qb);
     }
-    P.pix_to_face[pix] = best >= 0 ? (int64_t)n * P.F + best : -1;
+    if (!SHADE || P.pix_to_face) P.pix_to_face[pix] = best >= 0 ? (int64_t)n * P.F + best : -1;
     if (P.zbuf) P.zbuf[pix] = best >= 0 ? qb.z : -1.f;
     if (P.bary) {
         P.bary[3 * pix + 0] = best >= 0 ? qb.p[0] : -1.f;
@@ -316,6 +352,55 @@ __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
             P.render[out0 + c * plane] = o;
         }
     }
+    if constexpr (SHADE) {
+        float* out = P.image + 3 * pix;
+        if (best < 0) {
+            for (int c = 0; c < 3; ++c) out[c] = P.sh.background[c];
+            return;
+        }
+        // the winner passed mesh_prep, so its three indices are in [0, V)
+        float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; ++k) {
+            const size_t o = ((size_t)n * P.V + P.faces[3 * best + k]) * 3;
+            for (int d = 0; d < 3; ++d) {
+                pos[d] += qb.p[k] * P.verts[o + d];
+                nrm[d] += qb.p[k] * P.normals[o + d];
+            }
+        }
+        float rgb[3];
+        phong(P.sh, pos, nrm, rgb);
+        for (int c = 0; c < 3; ++c) out[c] = rgb[c];
+    }
+}
+
+// ---- vertex normals ------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(BLOCK) mesh_vertex_normals(Params P) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (int64_t)P.N * P.V) return;
+    const int n = (int)(i / P.V), v = (int)(i % P.V);
+    const float* verts = P.verts + (size_t)n * P.V * 3;
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int e = P.offsets[v]; e < P.offsets[v + 1]; ++e) {
+        const int fc = P.entries[e];
+        if (fc < 0 || fc >= 3 * P.F) continue;
+        const int f = fc / 3, k = fc % 3;
+        const int a = P.faces[3 * f + k], b = P.faces[3 * f + (k + 1) % 3], c = P.faces[3 * f + (k + 2) % 3];
+        if (a < 0 || a >= P.V || b < 0 || b >= P.V || c < 0 || c >= P.V) continue;
+        // corner k adds (v_{k+1} - v_k) x (v_{k+2} - v_k)
+        const float* pa = verts + 3 * (size_t)a;
+        const float* pb = verts + 3 * (size_t)b;
+        const float* pc = verts + 3 * (size_t)c;
+        const float e1[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
+        const float e2[3] = {pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2]};
+        s[0] += e1[1] * e2[2] - e1[2] * e2[1];
+        s[1] += e1[2] * e2[0] - e1[0] * e2[2];
+        s[2] += e1[0] * e2[1] - e1[1] * e2[0];
+    }
+    normalize3(s);
+    P.normals_out[3 * i + 0] = s[0];
+    P.normals_out[3 * i + 1] = s[1];
+    P.normals_out[3 * i + 2] = s[2];
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -485,6 +570,19 @@ int fill(const ExaMeshGeometry* g, const ExaMeshTexture* tex, Params& P) {
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
+// mesh_prep + mesh_bin of a forward (nothing to do without faces)
+int launch_prep_bin(const Params& P, hipStream_t st) {
+    const int64_t nf = (int64_t)P.N * P.F;
+    if (nf == 0) return 0;
+    hipLaunchKernelGGL(mesh_prep, dim3(blocks_for(nf)), dim3(BLOCK), 0, st, P);
+    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_prep");
+    hipLaunchKernelGGL(mesh_bin, dim3(blocks_for((int64_t)P.N * P.words * P.cells)), dim3(BLOCK), 0, st, P);
+    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bin");
+    return 0;
+}
+
+dim3 raster_grid(const Params& P) { return dim3((P.W + TILE - 1) / TILE, (P.H + TILE - 1) / TILE, P.N); }
+
 }  // namespace exa_mesh_impl
 
 using namespace exa_mesh_impl;
@@ -533,14 +631,8 @@ int exa_mesh_forward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, void* 
     P.bins = static_cast<uint32_t*>(bin_ws);
     P.pix_to_face = pix_to_face; P.zbuf = zbuf; P.bary = bary; P.render = render;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t nf = (int64_t)P.N * P.F;
-    if (nf > 0) {
-        hipLaunchKernelGGL(mesh_prep, dim3(blocks_for(nf)), dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_prep");
-        hipLaunchKernelGGL(mesh_bin, dim3(blocks_for((int64_t)P.N * P.words * P.cells)), dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bin");
-    }
-    const dim3 grid((P.W + TILE - 1) / TILE, (P.H + TILE - 1) / TILE, P.N);
+    if (int rc = launch_prep_bin(P, st)) return rc;
+    const dim3 grid = raster_grid(P);
     if (tex)
         hipLaunchKernelGGL(mesh_raster_fwd<true>, grid, dim3(BLOCK), 0, st, P);
     else
@@ -577,6 +669,48 @@ int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const
     }
     hipLaunchKernelGGL(mesh_bwd_gather, dim3(blocks_for(nv)), dim3(BLOCK), 0, st, P);
     if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bwd_gather");
+    return 0;
+}
+
+int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offsets, const int32_t* vert_entries,
+                            float* normals, void* stream) {
+    if (!g) return fail(EXA_MESH_E_NULLPTR, "geometry is NULL");
+    if (int rc = check_shape(g->N, g->V, g->F, 0, 0)) return rc;       // H, W, focal and princpt are not used
+    if (g->N < 1) return fail(EXA_MESH_E_INVALID, "N must be at least 1");
+    if (g->V == 0) return 0;
+    if (!normals || !vert_offsets || !g->verts) return fail(EXA_MESH_E_NULLPTR, "normals / vert_offsets / verts is NULL");
+    if (g->F > 0 && (!vert_entries || !g->faces)) return fail(EXA_MESH_E_NULLPTR, "vert_entries / faces is NULL");
+    Params P;
+    memset(&P, 0, sizeof(P));
+    P.N = g->N; P.V = g->V; P.F = g->F;
+    P.verts = g->verts; P.faces = g->faces;
+    P.offsets = vert_offsets; P.entries = vert_entries; P.normals_out = normals;
+    hipLaunchKernelGGL(mesh_vertex_normals, dim3(blocks_for((int64_t)P.N * P.V)), dim3(BLOCK), 0,
+                       static_cast<hipStream_t>(stream), P);
+    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_vertex_normals");
+    return 0;
+}
+
+int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shading, const float* normals, void* face_ws,
+                            void* bin_ws, int64_t* pix_to_face, float* zbuf, float* image, void* stream) {
+    Params P;
+    if (int rc = fill(g, nullptr, P)) return rc;
+    if (P.N < 1) return fail(EXA_MESH_E_INVALID, "N must be at least 1");
+    if (!shading) return fail(EXA_MESH_E_NULLPTR, "shading is NULL");
+    if (!(shading->shininess >= 0.f) || !isfinite(shading->shininess))
+        return fail(EXA_MESH_E_INVALID, "shininess must be finite and >= 0");
+    if (!image) return fail(EXA_MESH_E_NULLPTR, "image is NULL");
+    if (P.F > 0 && (!normals || !face_ws || !bin_ws)) return fail(EXA_MESH_E_NULLPTR, "normals / workspace is NULL");
+    if ((int64_t)P.H * P.W == 0) return 0;
+    P.recs = static_cast<FaceRec*>(face_ws);
+    P.bins = static_cast<uint32_t*>(bin_ws);
+    P.pix_to_face = pix_to_face; P.zbuf = zbuf; P.image = image;
+    P.normals = normals;
+    P.sh = *shading;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = launch_prep_bin(P, st)) return rc;
+    hipLaunchKernelGGL((mesh_raster_fwd<false, true>), raster_grid(P), dim3(BLOCK), 0, st, P);
+    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_raster_fwd (shaded)");
     return 0;
 }
 

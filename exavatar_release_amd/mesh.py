@@ -3,6 +3,9 @@
 * ``MeshRenderer(vertex_uv, face_uv)`` -- reference ``avatar/common/nets/layer.py:40-68`` (pytorch3d ``MeshRasterizer`` +
   ``TexturesUV``).  ``forward(uvmap, mesh, face, cam_param, render_shape)`` -> ``[N, C, H, W]``, -1 in every channel of a
   background pixel; differentiable in ``mesh`` (and through the PyTorch world->camera ``bmm`` in ``R`` / ``t``).
+* ``render_mesh(mesh, face, cam_param, bkg, blend_ratio=1.0)`` -- reference ``avatar/common/utils/vis.py:73-109`` and
+  ``fitting/common/utils/vis.py:18-53`` (pytorch3d ``SoftPhongShader``): the Phong-shaded mesh over ``bkg``, a numpy
+  [H,W,3] array.  Forward only, like ``shade_mesh`` (the device part) and ``vertex_normals`` under it.
 * ``get_face_index_map_xy(mesh, face, cam_param, render_shape)`` -- reference ``layer.py:23-38``: a ``Fragments``
   namedtuple.  ``pix_to_face`` [N,H,W,1] int64 holds packed ``n * F + f`` (-1: no face); ``zbuf`` [N,H,W,1] and
   ``bary_coords`` [N,H,W,1,3] are differentiable in ``mesh`` (-1 at background pixels); ``dists`` is ``None`` (the
@@ -44,6 +47,29 @@ reference's signature and ``forward`` repeats the second flip, so both compose a
 evaluated as F.grid_sample does (``0 + v_nw nw + v_ne ne + v_sw sw + v_se se``, weights from ``ix_se - ix`` etc.)
 without fused multiply-adds, so ``render[:, 3:] == 1`` (the reference's face mask, model.py:200) agrees with what
 PyTorch computes from the same uv.  1 .. 8 channels; the texture is a fixed buffer (no texture gradient).
+
+Phong-shaded render (reference ``render_mesh``, ``avatar/common/utils/vis.py:73-109`` and its numpy twin in
+``fitting/common/utils/vis.py:18-53``: pytorch3d ``SoftPhongShader`` + ``PointLights()`` + ``Materials(specular_color=0,
+shininess=0)`` + ``TexturesVertex`` of ones).  Rasterization is the one above, unchanged.  Negating x and y is a
+rotation, so every dot product of the shader is evaluated in the caller's camera frame: pytorch3d's default light at
+(0, 1, 0) is (0, -1, 0) here, and the camera centre is the origin.
+  * Vertex normals (pytorch3d ``_compute_vertex_normals``): corner k of every face -- culled and hidden faces included --
+    adds ``cross(v_{k+1} - v_k, v_{k+2} - v_k)``; each sum is normalised as ``x / max(|x|, 1e-6)`` (a vertex whose faces
+    are all degenerate keeps a zero normal).
+  * At a covered pixel, with the nearest face's corners k and its perspective-correct barycentrics b':
+    ``p = sum b'_k v_k``, ``n = sum b'_k n_k``, ``l^ = normalize(L - p)``, ``n^ = normalize(n)``, ``cos = n^ . l^``,
+    ``v^ = normalize(-p)``, ``r = -l^ + 2 cos n^``;
+    ``colour = La Ma + Ld Md relu(cos) + Ls Ms (relu(v^ . r) [cos > 0]) ** shininess`` per channel (``0 ** 0 = 1``,
+    as ``torch.pow``).  There is no flip of the normal towards the viewer: the winding decides which side is lit.  The
+    reference's constants give ``0.5 + 0.3 relu(cos)``, grey.
+  * Blend: for one face per pixel pytorch3d's ``softmax_rgb_blend`` (sigma = gamma = 1e-4, znear 1, zfar 100) returns
+    the shaded colour to ~1e-10 wherever 0 < z < 100, and the background colour (1, 1, 1) at empty pixels; that is what
+    the kernel writes.  At z >= zfar pytorch3d mixes in the background with a weight that depends on its ``dists``, which
+    this rasterizer does not compute: not reproduced (an avatar is a few metres from the camera).  The alpha channel is
+    not produced (the reference keeps ``images[..., :3]``).
+  * ``render_mesh`` then applies the reference's composite in numpy as written: ``is_bkg = zbuf <= 0`` (the same pixels
+    as ``pix_to_face == -1``), ``fg = render * blend_ratio + bkg / 255 * (1 - blend_ratio)``, ``fg * (1 - is_bkg) * 255
+    + bkg * is_bkg``.
 """
 import collections
 import ctypes
@@ -239,3 +265,120 @@ class MeshRenderer(nn.Module):
         focal, princpt = _camera(cam_param, N, mesh.device)
         render, _ = _RenderMesh.apply(mesh, topo, focal, princpt, render_height, render_width, texture, face_uvs)
         return render
+
+
+# ---- Phong-shaded render (reference render_mesh) -------------------------------------------------------------------------
+def _forward_only(mesh, what):
+    if torch.is_grad_enabled() and mesh.requires_grad:
+        raise NotImplementedError('%s is forward only (the reference renders under torch.no_grad()); pass mesh.detach() '
+                                  'or call it under torch.no_grad()' % what)
+
+
+def _vertex_normals(verts, topo):
+    faces, offsets, entries = topo
+    normals = torch.empty_like(verts)
+    g = _lib.ExaMeshGeometry(verts.shape[0], verts.shape[1], faces.shape[0], 0, 0, verts.data_ptr(), faces.data_ptr(),
+                             None, None)
+    with torch.cuda.device(verts.device):
+        _lib.check_mesh(_lib.load().exa_mesh_vertex_normals(ctypes.byref(g), _ptr(offsets), _ptr(entries), _ptr(normals),
+                                                            _stream_ptr(verts.device)))
+    return normals
+
+
+def _verts(mesh, what):
+    if isinstance(mesh, torch.Tensor) and mesh.dim() == 2:
+        mesh = mesh[None]
+    _check_mesh(mesh, what)
+    _forward_only(mesh, what)
+    return mesh.detach().to(torch.float32).contiguous()
+
+
+def vertex_normals(mesh, face):
+    """Area-weighted vertex normals of ``mesh`` [N,V,3] (or [V,3]) with faces ``face`` [F,3] (numpy or tensor): pytorch3d
+    ``Meshes.verts_normals_packed`` per mesh, [N,V,3] on the mesh's device.  Forward only."""
+    verts = _verts(mesh, 'vertex_normals')
+    return _vertex_normals(verts, _topology(face, verts.shape[1], verts.device))
+
+
+def _rgb(x, what):
+    v = np.asarray(x, dtype=np.float64)
+    if v.shape not in ((), (3,)) or not np.isfinite(v).all():
+        raise ValueError('shade_mesh: %s must be a finite scalar or RGB triple' % what)
+    return np.broadcast_to(v, (3,)).tolist()
+
+
+def _shading(light_location, lights, materials, shininess, background):
+    loc = np.asarray(light_location, dtype=np.float64)
+    if loc.shape != (3,) or not np.isfinite(loc).all():
+        raise ValueError('shade_mesh: light_location must be a finite (x, y, z)')
+    if len(lights) != 3 or len(materials) != 3:
+        raise ValueError('shade_mesh: lights and materials are (ambient, diffuse, specular)')
+    sh = _lib.ExaMeshShading()
+    sh.light_location[:] = loc.tolist()
+    sh.light_ambient[:], sh.light_diffuse[:], sh.light_specular[:] = [_rgb(c, 'lights[%d]' % i) for i, c in enumerate(lights)]
+    sh.material_ambient[:], sh.material_diffuse[:], sh.material_specular[:] = \
+        [_rgb(c, 'materials[%d]' % i) for i, c in enumerate(materials)]
+    sh.shininess = float(shininess)
+    sh.background[:] = _rgb(background, 'background')
+    return sh
+
+
+def shade_mesh(mesh, face, cam_param, render_shape, *, light_location=(0.0, -1.0, 0.0), lights=(0.5, 0.3, 0.2),
+               materials=(1.0, 1.0, 0.0), shininess=0.0, background=(1.0, 1.0, 1.0)):
+    """Phong-shaded render of the camera-space ``mesh`` [N,V,3] or [V,3] (faces ``face`` [F,3], one topology for all N)
+    seen by the pinhole cameras ``cam_param['focal']`` / ``['princpt']`` ([N,2] or [2]) at ``render_shape`` = (H, W):
+    the device half of the reference's ``render_mesh`` (module docstring).  ``light_location`` is in the caller's camera
+    frame; ``lights`` = (ambient, diffuse, specular) light colours and ``materials`` = (ambient, diffuse, specular)
+    material colours, each a scalar or an RGB triple; ``shininess`` >= 0.  The defaults are the reference's
+    ``PointLights()`` and ``Materials(specular_color=0, shininess=0)``.  N meshes go in one launch.
+
+    Returns ``(image [N,H,W,3] float32, background colour at empty pixels; pix_to_face [N,H,W] int64, packed n * F + f,
+    -1 at empty pixels)``.  Forward only: raises NotImplementedError for a ``mesh`` that requires grad under grad mode."""
+    verts = _verts(mesh, 'shade_mesh')
+    sh = _shading(light_location, lights, materials, shininess, background)
+    H, W = int(render_shape[0]), int(render_shape[1])
+    N, V = verts.shape[0], verts.shape[1]
+    device = verts.device
+    topo = _topology(face, V, device)
+    faces = topo[0]
+    focal, princpt = _camera(cam_param, N, device)
+    ws = _lib.mesh_workspace_sizes(N, faces.shape[0], H, W)
+    face_ws = torch.empty(int(ws.face_bytes), dtype=torch.uint8, device=device)
+    bin_ws = torch.empty(int(ws.bin_bytes), dtype=torch.uint8, device=device)
+    normals = _vertex_normals(verts, topo)
+    image = torch.empty((N, H, W, 3), dtype=torch.float32, device=device)
+    pix_to_face = torch.empty((N, H, W), dtype=torch.int64, device=device)
+    g = _geometry(verts, faces, focal, princpt, H, W)
+    with torch.cuda.device(device):
+        _lib.check_mesh(_lib.load().exa_mesh_forward_shaded(ctypes.byref(g), ctypes.byref(sh), _ptr(normals),
+                                                            _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), None,
+                                                            _ptr(image), _stream_ptr(device)))
+    return image, pix_to_face
+
+
+def _composite(render, is_bkg, bkg, blend_ratio):
+    """The last lines of the reference's ``render_mesh``, as written: numpy's dtype promotion is the reference's."""
+    fg = render * blend_ratio + bkg / 255 * (1 - blend_ratio)
+    return fg * (1 - is_bkg) * 255 + bkg * is_bkg
+
+
+def _host_array(x):
+    return np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
+
+
+def render_mesh(mesh, face, cam_param, bkg, blend_ratio=1.0):
+    """Drop-in for the reference's ``render_mesh`` (``avatar/common/utils/vis.py:73-109``, and the numpy-input copy in
+    ``fitting/common/utils/vis.py:18-53``): the camera-space ``mesh`` [V,3] (torch on any device, or numpy), ``face``
+    [F,3], ``cam_param['focal']`` / ``['princpt']`` [2] (torch or numpy; other keys are ignored), ``bkg`` a numpy
+    [H,W,3] image on a 0-255 scale that sets the render's size.  Shades on the current ROCm device, copies the image
+    and the background mask to the host and composites as the reference does; returns the numpy image (the callers
+    apply ``.astype(np.uint8)``)."""
+    device = torch.device('cuda', torch.cuda.current_device())
+    mesh = torch.as_tensor(_host_array(mesh) if not isinstance(mesh, torch.Tensor) else mesh)
+    mesh = mesh.to(device=device, dtype=torch.float32)
+    cam = {k: torch.as_tensor(_host_array(cam_param[k])) for k in ('focal', 'princpt')}
+    with torch.no_grad():
+        image, pix_to_face = shade_mesh(mesh[None], face, cam, (bkg.shape[0], bkg.shape[1]))
+    render = image[0].cpu().numpy()
+    is_bkg = (pix_to_face[0] == -1)[..., None].float().cpu().numpy()     # the reference's (zbuf <= 0): [H, W, 1]
+    return _composite(render, is_bkg, bkg, blend_ratio)

@@ -7,6 +7,10 @@
  * the conventions (projection, coverage, depth test, perspective-correct barycentrics, texture sampling) are written
  * out in that module's docstring.  It lives in the same `libexa_raster.so` as include/exa_raster.h.
  *
+ * The same raster also shades: `exa_mesh_vertex_normals` + `exa_mesh_forward_shaded` are the Phong-shaded mesh panel of
+ * the reference's `render_mesh` (avatar/common/utils/vis.py:73-109: pytorch3d `SoftPhongShader`, `PointLights`,
+ * `Materials`, `TexturesVertex` of ones), under `exavatar_release_amd.mesh.shade_mesh` / `render_mesh`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -57,6 +61,22 @@ typedef struct ExaMeshTexture {
     const float* face_uvs;              /* [dev] [F, 3, 2] */
 } ExaMeshTexture;
 
+/* Phong shading of a forward_shaded call (pytorch3d `phong_shading` with one point light and vertex colours of one).
+ * Every vector is in this header's camera frame (x right, y down, z forward); the camera centre is the origin.  At a
+ * covered pixel, with p and n the perspective-correct interpolations of the nearest face's positions and vertex
+ * normals, l^ = normalize(light_location - p), n^ = normalize(n), v^ = normalize(-p), cos = n^ . l^ (no flip towards the
+ * viewer: the winding decides which side is lit), r = -l^ + 2 cos n^:
+ *   colour = light_ambient * material_ambient + light_diffuse * material_diffuse * max(cos, 0)
+ *          + light_specular * material_specular * (max(v^ . r, 0) * [cos > 0]) ^ shininess        (0 ^ 0 = 1)
+ * per channel; normalize(x) = x / max(|x|, 1e-6).  Empty pixels get `background`. */
+typedef struct ExaMeshShading {
+    float light_location[3];
+    float light_ambient[3], light_diffuse[3], light_specular[3];
+    float material_ambient[3], material_diffuse[3], material_specular[3];
+    float shininess;                    /* >= 0 */
+    float background[3];
+} ExaMeshShading;
+
 typedef struct ExaMeshWorkspaceSizes {
     uint64_t face_bytes;                /* per-face screen records: written by forward, read by backward */
     uint64_t bin_bytes;                 /* per-cell face bitmasks: forward only */
@@ -93,6 +113,25 @@ int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const
                       const int64_t* pix_to_face, const float* dL_dzbuf, const float* dL_dbary, const float* dL_drender,
                       const int32_t* vert_offsets, const int32_t* vert_entries, void* grad_ws, float* dL_dverts,
                       void* stream);
+
+/* Area-weighted vertex normals (pytorch3d `_compute_vertex_normals`): every face adds, at each corner k, the cross
+ * product (v_{k+1} - v_k) x (v_{k+2} - v_k) -- culled and hidden faces too -- and each sum is normalised as
+ * x / max(|x|, 1e-6).  Gathered over exa_mesh_vertex_faces' CSR in its fixed order: atomic-free, bit-deterministic.
+ * Uses g's N, V, F, verts and faces (H, W unused).
+ *   vert_offsets, vert_entries  [dev] the CSR of `faces`.
+ *   normals                     [dev] [N, V, 3], fully written (vertices no face uses get 0). */
+int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offsets, const int32_t* vert_entries,
+                            float* normals, void* stream);
+
+/* Rasterize N meshes (as exa_mesh_forward) and Phong-shade the nearest face of every pixel.
+ *   shading          HOST pointer: lights, materials, background.
+ *   normals          [dev] [N, V, 3]: exa_mesh_vertex_normals of the same verts.
+ *   face_ws, bin_ws  [dev] workspaces of exa_mesh_workspace_sizes (face_bytes, bin_bytes).
+ *   pix_to_face      [dev] [N, H, W] int64 or NULL: as exa_mesh_forward.
+ *   zbuf             [dev] [N, H, W] or NULL: as exa_mesh_forward.
+ *   image            [dev] [N, H, W, 3] (channel-last): the shaded colour, `background` at empty pixels (required). */
+int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shading, const float* normals, void* face_ws,
+                            void* bin_ws, int64_t* pix_to_face, float* zbuf, float* image, void* stream);
 
 #ifdef __cplusplus
 }
