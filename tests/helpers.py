@@ -208,3 +208,42 @@ def needle_scene():
     cam, bg = scenes.neutral_camera(H, W, focal=f), torch.rand(3, generator=g)
     G = torch.randn(3, H, W, generator=g)
     return a, H, W, cam, bg, G
+
+
+LOSS_CONTENT = ('uniform', 'photo', 'bright', 'white')
+
+
+def loss_content(kind, shape, seed=0):
+    """(x, y): a rendered image and its target, float32 [B, C, H, W] on the CPU, of one content class of the image-loss
+    tests.  'uniform': independent U(0, 1).  'photo': ramps, a hard edge, exact 0 and 1 flats, a textured patch, and
+    x == y bit for bit on the left third.  'bright': 0.98 +- 0.002 with the target within 0.001 (sigma^2 = E[x^2] - mu^2
+    cancels).  'white': 1 - U(0, 0.004) with a third of the pixels exactly 1."""
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+
+    def r():
+        return torch.rand(shape, generator=g)
+    if kind == 'uniform':
+        return r(), r()
+    if kind == 'bright':
+        x = 0.98 + 0.002 * (2 * r() - 1)
+        return x, x + 0.001 * (2 * r() - 1)
+    if kind == 'white':
+        x, y = 1 - 0.004 * r(), 1 - 0.004 * r()
+        x[r() < 0.33] = 1.0
+        y[r() < 0.33] = 1.0
+        return x, y
+    assert kind == 'photo', kind
+    yy = torch.linspace(0, 1, H)[:, None]
+    xx = torch.linspace(0, 1, W)[None, :]
+    base = (0.15 + 0.5 * (0.7 * xx + 0.3 * yy)).expand(B, C, H, W).clone()
+    base += 0.05 * torch.arange(C, dtype=torch.float32)[None, :, None, None]
+    base[..., :, (2 * W) // 3:] += 0.2                                       # hard vertical edge
+    base[..., H // 4:H // 2 + 1, W // 2:(3 * W) // 4 + 1] = 1.0              # exact flats
+    base[..., (3 * H) // 4:, :W // 4 + 1] = 0.0
+    tex = (yy * H // 3 + xx * W // 3).floor().remainder(2).bool().expand(B, C, H, W)
+    base = torch.where(tex & (base > 0.0) & (base < 1.0), base + 0.1 * r(), base).clamp(0, 1)
+    x = (base + 0.03 * (r() - 0.5)).clamp(0, 1)
+    keep = (base == 0.0) | (base == 1.0)
+    keep[..., :, :W // 3] = True                                             # x == y bit for bit
+    return torch.where(keep, base, x), base
