@@ -12,6 +12,10 @@ and for the face render (pytorch3d ``MeshRasterizer`` + ``TexturesUV`` at refere
 and for the Phong-shaded mesh panel (pytorch3d ``SoftPhongShader`` in reference ``avatar/common/utils/vis.py:73-109``):
 
     from exavatar_release_amd import render_mesh
+
+and for the nearest-vertex search (pytorch3d ``knn_points`` at reference ``avatar/common/nets/module.py:86,543``):
+
+    from exavatar_release_amd import knn_points
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -21,9 +25,10 @@ from .renderer import ITERATION_RENDERS, GaussianRenderer, GraphedRenderer, rend
 from .graphed import GraphedIteration
 from .static import StaticRender, required_capacity
 from .mesh import Fragments, MeshRenderer, get_face_index_map_xy, render_mesh, shade_mesh, vertex_normals
+from .knn import knn_points
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
-           'vertex_normals', 'shade_mesh', 'render_mesh']
+           'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points']

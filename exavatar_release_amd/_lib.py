@@ -194,6 +194,17 @@ MESH_SIGNATURES = {
                                                c_void_p]),
 }
 
+# ---- the K-nearest-neighbour search (include/exa_knn.h): its own table, like the mesh functions
+KNN_NO_CULL = 1      # EXA_KNN_NO_CULL
+KNN_SIGNATURES = {
+    'exa_knn_version': (ctypes.c_int, []),
+    'exa_knn_last_error': (ctypes.c_char_p, []),
+    'exa_knn_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_knn_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, _U64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exa_knn_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 9 + [c_void_p]),
+}
+
 _lib = None
 
 
@@ -213,7 +224,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in MESH_SIGNATURES.items():
+    for name, (res, args) in list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -233,6 +244,18 @@ def check_mesh(rc):
     if rc != 0:
         msg = load().exa_mesh_last_error()
         raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_mesh error', rc))
+
+
+def check_knn(rc):
+    if rc != 0:
+        msg = load().exa_knn_last_error()
+        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_knn error', rc))
+
+
+def knn_workspace_size(N, P1, P2, K):
+    out = _U64()
+    check_knn(load().exa_knn_workspace_size(N, P1, P2, K, ctypes.byref(out)))
+    return int(out.value)
 
 
 def mesh_workspace_sizes(N, F, H, W):

@@ -36,6 +36,8 @@ SOURCES = {
     'api.hip': [],
     # the face render's bilinear blend must round as F.grid_sample's does (the reference tests `mask == 1`)
     'mesh_raster.hip': ['-ffp-contract=off'],
+    # knn_points' distances are defined operation by operation (include/exa_knn.h): no contraction into FMAs
+    'knn.hip': ['-ffp-contract=off'],
 }
 
 
@@ -58,7 +60,7 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    for hdr in ('exa_raster.h', 'exa_mesh.h'):
+    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h'):
         with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
             h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())

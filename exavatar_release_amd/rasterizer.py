@@ -89,6 +89,7 @@ class _Config:
     compose_reuse_source = True   # composite renders copy source A's pixels where source B has no entry (developer A/B knob)
     upstream_scale_grad = False   # True: dL/dscale as upstream returns it (w.r.t. scale_modifier * scale, i.e. divided
     #                               by scale_modifier); identical for the reference, which passes 1.0 (module.py:615)
+    knn_cull = True               # knn_points: cull ref chunks by their boxes (False: visit every ref; the same bits either way)
     poison = False                # debug: fill every workspace with 0xFF before the kernels see it (the library promises to write
     #                               every section before it reads it; tests run under it with EXA_TEST_POISON=1)
     compiled_node = 'auto'        # single renders through the compiled autograd node (csrc/torch_binding.cpp -> _exa_torch.so: the
