@@ -16,6 +16,11 @@ and for the Phong-shaded mesh panel (pytorch3d ``SoftPhongShader`` in reference 
 and for the nearest-vertex search (pytorch3d ``knn_points`` at reference ``avatar/common/nets/module.py:86,543``):
 
     from exavatar_release_amd import knn_points
+
+and for the triplane feature lookup (``F.grid_sample`` in ``extract_tri_feature``, reference
+``avatar/common/nets/module.py:424-457``):
+
+    from exavatar_release_amd import TriplaneFeatures
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -26,9 +31,10 @@ from .graphed import GraphedIteration
 from .static import StaticRender, required_capacity
 from .mesh import Fragments, MeshRenderer, get_face_index_map_xy, render_mesh, shade_mesh, vertex_normals
 from .knn import knn_points
+from .triplane import TriplaneFeatures
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
-           'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points']
+           'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures']

@@ -205,6 +205,15 @@ KNN_SIGNATURES = {
     'exa_knn_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 9 + [c_void_p]),
 }
 
+# ---- the triplane feature lookup (include/exa_triplane.h): its own table
+TRIPLANE_SIGNATURES = {
+    'exa_triplane_version': (ctypes.c_int, []),
+    'exa_triplane_last_error': (ctypes.c_char_p, []),
+    'exa_triplane_plan_keys': (ctypes.c_int, [_I32, _I32, _I32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exa_triplane_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 6),
+    'exa_triplane_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 6 + [_I32, _I32] + [c_void_p] * 3),
+}
+
 _lib = None
 
 
@@ -224,7 +233,8 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
+    for name, (res, args) in (list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) +
+                              list(TRIPLANE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -250,6 +260,12 @@ def check_knn(rc):
     if rc != 0:
         msg = load().exa_knn_last_error()
         raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_knn error', rc))
+
+
+def check_triplane(rc):
+    if rc != 0:
+        msg = load().exa_triplane_last_error()
+        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_triplane error', rc))
 
 
 def knn_workspace_size(N, P1, P2, K):

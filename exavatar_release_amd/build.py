@@ -38,6 +38,8 @@ SOURCES = {
     'mesh_raster.hip': ['-ffp-contract=off'],
     # knn_points' distances are defined operation by operation (include/exa_knn.h): no contraction into FMAs
     'knn.hip': ['-ffp-contract=off'],
+    # the triplane lookup and its backward are defined operation by operation (include/exa_triplane.h)
+    'triplane.hip': ['-ffp-contract=off'],
 }
 
 
@@ -60,7 +62,7 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h'):
+    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h'):
         with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
             h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())
