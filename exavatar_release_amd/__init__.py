@@ -21,6 +21,11 @@ and for the triplane feature lookup (``F.grid_sample`` in ``extract_tri_feature`
 ``avatar/common/nets/module.py:424-457``):
 
     from exavatar_release_amd import TriplaneFeatures
+
+and for the linear blend skinning that poses the Gaussians (``get_transform_mat_vertex`` + ``lbs`` + the camera -> world
+step, reference ``avatar/common/nets/module.py:413-422,548-556``):
+
+    from exavatar_release_amd import skin_points
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -32,9 +37,11 @@ from .static import StaticRender, required_capacity
 from .mesh import Fragments, MeshRenderer, get_face_index_map_xy, render_mesh, shade_mesh, vertex_normals
 from .knn import knn_points
 from .triplane import TriplaneFeatures
+from .skinning import skin_points
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
-           'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures']
+           'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
+           'skin_points']

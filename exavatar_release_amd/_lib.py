@@ -214,6 +214,17 @@ TRIPLANE_SIGNATURES = {
     'exa_triplane_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 6 + [_I32, _I32] + [c_void_p] * 3),
 }
 
+# ---- the linear blend skinning (include/exa_skin.h): its own table
+_PP = ctypes.POINTER(c_void_p)       # host array of S device pointers
+SKIN_SIGNATURES = {
+    'exa_skin_version': (ctypes.c_int, []),
+    'exa_skin_last_error': (ctypes.c_char_p, []),
+    'exa_skin_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_skin_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32, _PP] + [c_void_p] * 6 + [_PP, c_void_p]),
+    'exa_skin_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32, _PP] + [c_void_p] * 4 + [_PP, _PP, c_void_p, c_void_p,
+                                                                                        c_void_p, _U64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -234,7 +245,7 @@ def load():
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in (list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) +
-                              list(TRIPLANE_SIGNATURES.items())):
+                              list(TRIPLANE_SIGNATURES.items()) + list(SKIN_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -266,6 +277,18 @@ def check_triplane(rc):
     if rc != 0:
         msg = load().exa_triplane_last_error()
         raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_triplane error', rc))
+
+
+def check_skin(rc):
+    if rc != 0:
+        msg = load().exa_skin_last_error()
+        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_skin error', rc))
+
+
+def skin_workspace_size(V, J):
+    out = _U64()
+    check_skin(load().exa_skin_workspace_size(V, J, ctypes.byref(out)))
+    return int(out.value)
 
 
 def knn_workspace_size(N, P1, P2, K):

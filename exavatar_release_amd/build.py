@@ -40,6 +40,8 @@ SOURCES = {
     'knn.hip': ['-ffp-contract=off'],
     # the triplane lookup and its backward are defined operation by operation (include/exa_triplane.h)
     'triplane.hip': ['-ffp-contract=off'],
+    # the skinning and its backward are defined operation by operation (include/exa_skin.h)
+    'skinning.hip': ['-ffp-contract=off'],
 }
 
 
@@ -62,7 +64,7 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h'):
+    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h', 'exa_skin.h'):
         with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
             h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())
