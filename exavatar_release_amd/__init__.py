@@ -26,6 +26,11 @@ and for the linear blend skinning that poses the Gaussians (``get_transform_mat_
 step, reference ``avatar/common/nets/module.py:413-422,548-556``):
 
     from exavatar_release_amd import skin_points
+
+and for the four MLPs between them (``make_linear_layers(..., use_gn=True)`` + heads, reference
+``avatar/common/nets/module.py:279-287,459-509,524-528``):
+
+    from exavatar_release_amd import FusedMLP
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -38,10 +43,11 @@ from .mesh import Fragments, MeshRenderer, get_face_index_map_xy, render_mesh, s
 from .knn import knn_points
 from .triplane import TriplaneFeatures
 from .skinning import skin_points
+from .mlp import FusedMLP
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
-           'skin_points']
+           'skin_points', 'FusedMLP']

@@ -225,6 +225,16 @@ SKIN_SIGNATURES = {
                                                                                         c_void_p, _U64, c_void_p]),
 }
 
+# ---- the fused MLP (include/exa_mlp.h): its own table; the net travels as a struct (mlp.ExaMlpNet)
+MLP_SIGNATURES = {
+    'exa_mlp_version': (ctypes.c_int, []),
+    'exa_mlp_last_error': (ctypes.c_char_p, []),
+    'exa_mlp_param_count': (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'exa_mlp_workspace_size': (ctypes.c_int, [c_void_p, _I32, ctypes.POINTER(_U64)]),
+    'exa_mlp_forward': (ctypes.c_int, [c_void_p, _I32, c_void_p, _PP, c_void_p]),
+    'exa_mlp_backward': (ctypes.c_int, [c_void_p, _I32, c_void_p, _PP] + [c_void_p] * 4 + [_U64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -245,7 +255,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     for name, (res, args) in (list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) +
-                              list(TRIPLANE_SIGNATURES.items()) + list(SKIN_SIGNATURES.items())):
+                              list(TRIPLANE_SIGNATURES.items()) + list(SKIN_SIGNATURES.items()) +
+                              list(MLP_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -283,6 +294,12 @@ def check_skin(rc):
     if rc != 0:
         msg = load().exa_skin_last_error()
         raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_skin error', rc))
+
+
+def check_mlp(rc):
+    if rc != 0:
+        msg = load().exa_mlp_last_error()
+        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_mlp error', rc))
 
 
 def skin_workspace_size(V, J):

@@ -42,6 +42,8 @@ SOURCES = {
     'triplane.hip': ['-ffp-contract=off'],
     # the skinning and its backward are defined operation by operation (include/exa_skin.h)
     'skinning.hip': ['-ffp-contract=off'],
+    # the fused MLP's VALU arithmetic (GroupNorm, its backward) is defined operation by operation (include/exa_mlp.h)
+    'mlp.hip': ['-ffp-contract=off'],
 }
 
 
@@ -64,7 +66,7 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h', 'exa_skin.h'):
+    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h', 'exa_skin.h', 'exa_mlp.h'):
         with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
             h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())
