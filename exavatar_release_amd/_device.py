@@ -1,0 +1,65 @@
+"""What every feature module needs to hand torch tensors to the C ABIs: data pointers, the current stream, workspaces
+from the torch allocator, the ROCm-only guard, and the package's run-time ``config``."""
+import ctypes
+
+import torch
+
+
+class _Config:
+    mode = 'auto'             # 'auto' | 'exact' | 'capacity'
+    capacity_growth = 1.5     # capacity mode: head-room over the largest D seen so far
+    min_capacity = 1 << 16
+    fixed_capacity = None     # capacity mode: use exactly this many instances (e.g. calibrated by a warm-up); a list /
+    #                           tuple names one capacity per job of a batched call
+    keep_debug = False        # developer probes: keep the workspaces of the most recent forward reachable
+    on_overflow = 'retry'     # 'retry' | 'raise' (rasterizer module docstring)
+    overlap_composites = True     # INSIDE a stream capture: the composites' list merges run on a second stream while their sources
+    #                               blend (the calls are split at EXA_RASTER_STAGE_NO_BLEND; fork / join become graph edges).
+    #                               Eager calls never do this: the stream switches cost the host more than the overlap gives
+    fold_composite_grads = True   # a composite's gradients for source B are handed to B's own render, whose backward adds them
+    #                               inside its per-Gaussian kernel (ExaRasterBackwardJob.accumulate) instead of autograd
+    #                               summing the two with one kernel per tensor (developer A/B knob; same values bit for bit)
+    compose_reuse_source = True   # composite renders copy source A's pixels where source B has no entry (developer A/B knob)
+    upstream_scale_grad = False   # True: dL/dscale as upstream returns it (w.r.t. scale_modifier * scale, i.e. divided
+    #                               by scale_modifier); identical for the reference, which passes 1.0 (module.py:615)
+    knn_cull = True               # knn_points: cull ref chunks by their boxes (False: visit every ref; the same bits either way)
+    poison = False                # debug: fill every workspace with 0xFF before the kernels see it (the library promises to write
+    #                               every section before it reads it; tests run under it with EXA_TEST_POISON=1)
+    compiled_node = 'auto'        # single renders through the compiled autograd node (csrc/torch_binding.cpp -> _exa_torch.so: the
+    #                               same C-ABI calls, arena layouts and overflow protocol as rasterizer._Rasterize at a quarter of
+    #                               the host time): 'auto' = when it is built and the call is one it covers, 'off' = always the
+    #                               Python node, 'require' = raise if the extension is missing
+
+
+config = _Config()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _ptrs(tensors):
+    """Host array of device pointers (NULL for None)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def _addr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stream_ptr(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _workspace(nbytes, device):
+    """Uninitialised byte workspace (``config.poison``: filled with 0xFF, so that a kernel reading a section nobody
+    wrote sees the worst garbage instead of whatever the allocator left there)."""
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    if config.poison:
+        ws.fill_(255)
+    return ws
+
+
+def need_rocm(device, what):
+    if device.type != 'cuda':
+        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)

@@ -1,4 +1,4 @@
-"""ctypes binding of ``libexa_raster.so`` (C ABI declared in ``include/exa_raster.h``).
+"""ctypes binding of ``libexa_raster.so``: the C ABIs declared in ``include/exa_*.h``, one :class:`Abi` record each.
 
 The library is the product: if it is missing or fails to load this module raises -- there is no
 CPU / PyTorch fallback path anywhere in the package.
@@ -14,6 +14,7 @@ c_float_p = ctypes.c_void_p      # device pointers travel as plain addresses
 c_void_p = ctypes.c_void_p
 
 
+# ---- the structs the headers declare, field by field (tests/test_abi.py checks every size and offset against C)
 class ExaRasterSettings(ctypes.Structure):
     _fields_ = [
         ('image_height', ctypes.c_int32),
@@ -101,13 +102,78 @@ class ExaRasterBackwardJob(ctypes.Structure):
     ]
 
 
+class ExaMeshGeometry(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('verts', c_void_p), ('faces', c_void_p), ('focal', c_void_p), ('princpt', c_void_p)]
+
+
+class ExaMeshTexture(ctypes.Structure):
+    _fields_ = [('C', ctypes.c_int32), ('tex_H', ctypes.c_int32), ('tex_W', ctypes.c_int32), ('tex_N', ctypes.c_int32),
+                ('texture', c_void_p), ('face_uvs', c_void_p)]
+
+
+class ExaMeshWorkspaceSizes(ctypes.Structure):
+    _fields_ = [('face_bytes', ctypes.c_uint64), ('bin_bytes', ctypes.c_uint64), ('grad_bytes', ctypes.c_uint64)]
+
+
+class ExaMeshShading(ctypes.Structure):
+    _fields_ = [('light_location', ctypes.c_float * 3), ('light_ambient', ctypes.c_float * 3),
+                ('light_diffuse', ctypes.c_float * 3), ('light_specular', ctypes.c_float * 3),
+                ('material_ambient', ctypes.c_float * 3), ('material_diffuse', ctypes.c_float * 3),
+                ('material_specular', ctypes.c_float * 3), ('shininess', ctypes.c_float),
+                ('background', ctypes.c_float * 3)]
+
+
+class ExaMlpNet(ctypes.Structure):
+    """exa_mlp_net (include/exa_mlp.h): the arrays hold EXA_MLP_MAX_HEADS = 4 heads and EXA_MLP_MAX_LAYERS = 4 layers."""
+    _fields_ = [('n_layers', ctypes.c_int32), ('in_width', ctypes.c_int32), ('shared_width', ctypes.c_int32),
+                ('groups', ctypes.c_int32), ('n_heads', ctypes.c_int32), ('head_width', ctypes.c_int32 * 4),
+                ('ld_w0', ctypes.c_int32), ('ld_ws', ctypes.c_int32), ('eps', ctypes.c_float * 4),
+                ('W', ctypes.c_void_p * 4), ('b', ctypes.c_void_p * 4),
+                ('gamma', ctypes.c_void_p * 4), ('beta', ctypes.c_void_p * 4),
+                ('Ws', ctypes.c_void_p), ('shared', ctypes.c_void_p), ('Wh', ctypes.c_void_p), ('bh', ctypes.c_void_p)]
+
+
 STORE_CTX, STAGE_NO_BLEND, STAGE_BLEND_ONLY, STAGE_NO_SORT, STAGE_SORT_ONLY = 1, 2, 4, 8, 16       # bits of `store_ctx` (include/exa_raster.h, EXA_RASTER_STAGE_*)
 
-# symbol -> (restype, argtypes); must list every function include/exa_raster.h declares
+TIMING_SLOTS = 9
+KNN_NO_CULL = 1      # EXA_KNN_NO_CULL
+
+
+class Abi:
+    """One C ABI of the library: its header, its functions (symbol -> (restype, argtypes): every function the header
+    declares and nothing else), the version this binding is written against, and the header's structs mirrored above
+    (C name -> ctypes class).  ``check(rc)`` raises RuntimeError with this ABI's own ``*_last_error()`` text when rc is
+    not 0; it is a plain function, so that ``check = RASTER.check`` costs the raster hot path nothing."""
+
+    def __init__(self, prefix, header, version, signatures, structs=None):
+        self.prefix, self.header, self.version, self.signatures = prefix, header, version, signatures
+        self.structs = structs or {}
+        last_error = prefix + '_last_error'
+
+        def check(rc):
+            if rc != 0:
+                msg = getattr(load(), last_error)()
+                raise RuntimeError('%s (status %d)' % (msg.decode() if msg else prefix + ' error', rc))
+        self.check = check
+
+
+def _by_name(*classes):
+    return {c.__name__: c for c in classes}
+
+
 _I32 = ctypes.c_int32
 _U64 = ctypes.c_uint64
 _SP = ctypes.POINTER(ExaRasterSettings)
-SIGNATURES = {
+_GP = ctypes.POINTER(ExaMeshGeometry)
+_TP = ctypes.POINTER(ExaMeshTexture)
+_SHP = ctypes.POINTER(ExaMeshShading)
+_PP = ctypes.POINTER(c_void_p)       # host array of device pointers
+
+# ---- the six ABIs
+# the Gaussian rasterizer with its image losses (exa_ssim_*, exa_photo_*, exa_l1_* report through exa_raster_last_error)
+RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
     'exa_raster_version': (ctypes.c_int, []),
     'exa_raster_last_error': (ctypes.c_char_p, []),
     'exa_raster_workspace_sizes': (ctypes.c_int, [_I32, _I32, _I32, _U64, ctypes.POINTER(ExaRasterWorkspaceSizes)]),
@@ -149,39 +215,11 @@ SIGNATURES = {
     'exa_raster_timing_enable': (ctypes.c_int, [_I32]),
     'exa_raster_timing_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _I32]),
     'exa_raster_timing_name': (ctypes.c_char_p, [_I32]),
-}
-TIMING_SLOTS = 9
+}, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
+            ExaRasterBackwardJob))
 
-
-# ---- the triangle rasterizer of the face render (include/exa_mesh.h): its own table, so SIGNATURES stays the ABI of
-# exa_raster.h alone
-class ExaMeshGeometry(ctypes.Structure):
-    _fields_ = [('N', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32),
-                ('H', ctypes.c_int32), ('W', ctypes.c_int32),
-                ('verts', c_void_p), ('faces', c_void_p), ('focal', c_void_p), ('princpt', c_void_p)]
-
-
-class ExaMeshTexture(ctypes.Structure):
-    _fields_ = [('C', ctypes.c_int32), ('tex_H', ctypes.c_int32), ('tex_W', ctypes.c_int32), ('tex_N', ctypes.c_int32),
-                ('texture', c_void_p), ('face_uvs', c_void_p)]
-
-
-class ExaMeshWorkspaceSizes(ctypes.Structure):
-    _fields_ = [('face_bytes', ctypes.c_uint64), ('bin_bytes', ctypes.c_uint64), ('grad_bytes', ctypes.c_uint64)]
-
-
-class ExaMeshShading(ctypes.Structure):
-    _fields_ = [('light_location', ctypes.c_float * 3), ('light_ambient', ctypes.c_float * 3),
-                ('light_diffuse', ctypes.c_float * 3), ('light_specular', ctypes.c_float * 3),
-                ('material_ambient', ctypes.c_float * 3), ('material_diffuse', ctypes.c_float * 3),
-                ('material_specular', ctypes.c_float * 3), ('shininess', ctypes.c_float),
-                ('background', ctypes.c_float * 3)]
-
-
-_GP = ctypes.POINTER(ExaMeshGeometry)
-_TP = ctypes.POINTER(ExaMeshTexture)
-_SHP = ctypes.POINTER(ExaMeshShading)
-MESH_SIGNATURES = {
+# the triangle rasterizer of the face render
+MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
     'exa_mesh_workspace_sizes': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ExaMeshWorkspaceSizes)]),
@@ -192,55 +230,56 @@ MESH_SIGNATURES = {
     'exa_mesh_vertex_normals': (ctypes.c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_mesh_forward_shaded': (ctypes.c_int, [_GP, _SHP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
-}
+}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
 
-# ---- the K-nearest-neighbour search (include/exa_knn.h): its own table, like the mesh functions
-KNN_NO_CULL = 1      # EXA_KNN_NO_CULL
-KNN_SIGNATURES = {
+# the K-nearest-neighbour search
+KNN = Abi('exa_knn', 'exa_knn.h', 100, {
     'exa_knn_version': (ctypes.c_int, []),
     'exa_knn_last_error': (ctypes.c_char_p, []),
     'exa_knn_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(_U64)]),
     'exa_knn_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, _U64,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_knn_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 9 + [c_void_p]),
-}
+})
 
-# ---- the triplane feature lookup (include/exa_triplane.h): its own table
-TRIPLANE_SIGNATURES = {
+# the triplane feature lookup
+TRIPLANE = Abi('exa_triplane', 'exa_triplane.h', 100, {
     'exa_triplane_version': (ctypes.c_int, []),
     'exa_triplane_last_error': (ctypes.c_char_p, []),
     'exa_triplane_plan_keys': (ctypes.c_int, [_I32, _I32, _I32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_triplane_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 6),
     'exa_triplane_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32] + [c_void_p] * 6 + [_I32, _I32] + [c_void_p] * 3),
-}
+})
 
-# ---- the linear blend skinning (include/exa_skin.h): its own table
-_PP = ctypes.POINTER(c_void_p)       # host array of S device pointers
-SKIN_SIGNATURES = {
+# the linear blend skinning
+SKIN = Abi('exa_skin', 'exa_skin.h', 100, {
     'exa_skin_version': (ctypes.c_int, []),
     'exa_skin_last_error': (ctypes.c_char_p, []),
     'exa_skin_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
     'exa_skin_forward': (ctypes.c_int, [_I32, _I32, _I32, _I32, _PP] + [c_void_p] * 6 + [_PP, c_void_p]),
     'exa_skin_backward': (ctypes.c_int, [_I32, _I32, _I32, _I32, _PP] + [c_void_p] * 4 + [_PP, _PP, c_void_p, c_void_p,
                                                                                         c_void_p, _U64, c_void_p]),
-}
+})
 
-# ---- the fused MLP (include/exa_mlp.h): its own table; the net travels as a struct (mlp.ExaMlpNet)
-MLP_SIGNATURES = {
+# the fused MLP
+MLP = Abi('exa_mlp', 'exa_mlp.h', 100, {
     'exa_mlp_version': (ctypes.c_int, []),
     'exa_mlp_last_error': (ctypes.c_char_p, []),
     'exa_mlp_param_count': (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'exa_mlp_workspace_size': (ctypes.c_int, [c_void_p, _I32, ctypes.POINTER(_U64)]),
     'exa_mlp_forward': (ctypes.c_int, [c_void_p, _I32, c_void_p, _PP, c_void_p]),
     'exa_mlp_backward': (ctypes.c_int, [c_void_p, _I32, c_void_p, _PP] + [c_void_p] * 4 + [_U64, c_void_p]),
-}
+}, {'exa_mlp_net': ExaMlpNet})
+
+ABIS = (RASTER, MESH, KNN, TRIPLANE, SKIN, MLP)
+check = RASTER.check      # the raster hot path's one call per ctypes call: a direct alias, no lookup
 
 _lib = None
 
 
 def load():
-    """Load the shared library (once). ``torch`` must be imported first so that the HIP runtime that
-    torch bundles (SONAME libamdhip64.so.7) is the one the library binds to."""
+    """Load the shared library (once) and bind every ABI's functions.  ``torch`` must be imported first so that the HIP
+    runtime that torch bundles (SONAME libamdhip64.so.7) is the one the library binds to."""
     global _lib
     if _lib is not None:
         return _lib
@@ -250,73 +289,32 @@ def load():
             'exavatar_release_amd: %s is missing. Build it with `python -m exavatar_release_amd.build` '
             '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = ABI mismatch, fail loudly
-        fn.restype = res
-        fn.argtypes = args
-    for name, (res, args) in (list(MESH_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) +
-                              list(TRIPLANE_SIGNATURES.items()) + list(SKIN_SIGNATURES.items()) +
-                              list(MLP_SIGNATURES.items())):
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.exa_raster_version() < 139:
+    for abi in ABIS:
+        for name, (res, args) in abi.signatures.items():
+            fn = getattr(lib, name)          # AttributeError here = ABI mismatch, fail loudly
+            fn.restype = res
+            fn.argtypes = args
+    if lib.exa_raster_version() < RASTER.version:
         raise RuntimeError('exavatar_release_amd: libexa_raster.so is too old')
     _lib = lib
     return lib
 
 
-def check(rc):
-    if rc != 0:
-        msg = load().exa_raster_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_raster error', rc))
-
-
-def check_mesh(rc):
-    if rc != 0:
-        msg = load().exa_mesh_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_mesh error', rc))
-
-
-def check_knn(rc):
-    if rc != 0:
-        msg = load().exa_knn_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_knn error', rc))
-
-
-def check_triplane(rc):
-    if rc != 0:
-        msg = load().exa_triplane_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_triplane error', rc))
-
-
-def check_skin(rc):
-    if rc != 0:
-        msg = load().exa_skin_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_skin error', rc))
-
-
-def check_mlp(rc):
-    if rc != 0:
-        msg = load().exa_mlp_last_error()
-        raise RuntimeError('%s (status %d)' % (msg.decode() if msg else 'exa_mlp error', rc))
-
-
 def skin_workspace_size(V, J):
     out = _U64()
-    check_skin(load().exa_skin_workspace_size(V, J, ctypes.byref(out)))
+    SKIN.check(load().exa_skin_workspace_size(V, J, ctypes.byref(out)))
     return int(out.value)
 
 
 def knn_workspace_size(N, P1, P2, K):
     out = _U64()
-    check_knn(load().exa_knn_workspace_size(N, P1, P2, K, ctypes.byref(out)))
+    KNN.check(load().exa_knn_workspace_size(N, P1, P2, K, ctypes.byref(out)))
     return int(out.value)
 
 
 def mesh_workspace_sizes(N, F, H, W):
     out = ExaMeshWorkspaceSizes()
-    check_mesh(load().exa_mesh_workspace_sizes(N, F, H, W, ctypes.byref(out)))
+    MESH.check(load().exa_mesh_workspace_sizes(N, F, H, W, ctypes.byref(out)))
     return out
 
 

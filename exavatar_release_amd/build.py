@@ -4,6 +4,7 @@ Plain ``hipcc --offload-arch=gfx950`` on the ``.hip`` sources under ``csrc/``; n
 extension machinery, no torch headers (the library is a pure C ABI, include/exa_raster.h).
 The ``.so`` stays in-tree so it travels to the GPU box with the repo snapshot.
 """
+import glob
 import hashlib
 import os
 import shutil
@@ -66,8 +67,8 @@ def _digest():
         with open(os.path.join(CSRC, name), 'rb') as f:
             h.update(name.encode())
             h.update(f.read())
-    for hdr in ('exa_raster.h', 'exa_mesh.h', 'exa_knn.h', 'exa_triplane.h', 'exa_skin.h', 'exa_mlp.h'):
-        with open(os.path.join(HERE, '..', 'include', hdr), 'rb') as f:
+    for hdr in sorted(glob.glob(os.path.join(HERE, '..', 'include', 'exa_*.h'))):
+        with open(hdr, 'rb') as f:
             h.update(f.read())
     h.update(repr((COMMON, SOURCES)).encode())
     return h.hexdigest()

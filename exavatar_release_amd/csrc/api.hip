@@ -10,16 +10,7 @@ using namespace exa;
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_raster: %s", what);
-    return code;
-}
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_raster: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_raster")
 
 #define EXA_HIP(expr, where)                                   \
     do {                                                       \
@@ -607,8 +598,7 @@ int exa_raster_select_row(const float* table, int32_t n_rows, int32_t row_floats
     if (!table || !counter || !dst) return fail(EXA_RASTER_E_NULLPTR, "select_row: NULL pointer");
     if (n_rows <= 0 || row_floats <= 0) return fail(EXA_RASTER_E_INVALID, "select_row: n_rows and row_floats must be positive");
     select_row_kernel<<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(table, n_rows, row_floats, counter, dst);
-    EXA_HIP(hipGetLastError(), "select_row");
-    return 0;
+    return launched("select_row");
 }
 
 int exa_raster_store_pointers(void* table, const void* const* ptrs, int32_t n, void* stream) {
@@ -618,8 +608,7 @@ int exa_raster_store_pointers(void* table, const void* const* ptrs, int32_t n, v
     Ptr16 v;
     for (int i = 0; i < 16; ++i) v.p[i] = i < n ? ptrs[i] : nullptr;
     store_pointers_kernel<<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(static_cast<const void**>(table), v, n);
-    EXA_HIP(hipGetLastError(), "store_pointers");
-    return 0;
+    return launched("store_pointers");
 }
 
 int exa_raster_host_device_pointer(void* host_ptr, void** device_ptr_out) {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/exa_raster.h"
+#include "abi_status.h"
 
 namespace exa {
 
@@ -127,7 +128,6 @@ __host__ __device__ inline Grid make_grid(int W, int H) {
     return g;
 }
 
-__host__ __device__ inline uint64_t align256(uint64_t v) { return (v + 255) & ~uint64_t(255); }
 __host__ __device__ inline int num_chunks(int P) { return (P + CHUNK - 1) / CHUNK; }
 
 // Layout of the tile workspace (all sections 256-byte aligned).  Nothing in it needs zeroing by the caller or by

@@ -39,8 +39,12 @@
 #include <string.h>
 
 #include "../../include/exa_knn.h"
+#include "abi_status.h"
 
 namespace exa_knn_impl {
+
+using exa::align256;
+using exa::ceil_div;
 
 constexpr int WAVE = 64;
 constexpr int NPART = 64;                    // partial boxes per batch element (= one wave reduces them)
@@ -509,17 +513,7 @@ __global__ void __launch_bounds__(BLOCK) knn_grad_p2(BwdParams P) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_knn: %s", what);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_knn: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_knn")
 
 int check_shape(int32_t N, int32_t P1, int32_t P2, int32_t K) {
     if (N < 0 || P1 < 0 || P2 < 0) return fail(EXA_KNN_E_INVALID, "negative size");
@@ -528,8 +522,6 @@ int check_shape(int32_t N, int32_t P1, int32_t P2, int32_t K) {
     if (K < 1 || K > EXA_KNN_MAX_K) return fail(EXA_KNN_E_INVALID, "K must be 1 .. 32");
     return 0;
 }
-
-uint64_t align256(uint64_t n) { return (n + 255) & ~(uint64_t)255; }
 
 // byte offsets of the workspace sections; total 0 when there is nothing to search
 struct Layout {
@@ -553,35 +545,30 @@ Layout layout(int32_t N, int32_t P1, int32_t P2) {
     return L;
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 template <int KK>
 int launch_search(const Params& P, bool cull, hipStream_t st) {
-    const dim3 grid((P.P1 + WAVE - 1) / WAVE, P.N);
+    const dim3 grid(ceil_div(P.P1, WAVE), P.N);
     if (cull)
         hipLaunchKernelGGL((knn_search<KK, true>), grid, dim3(WAVE), 0, st, P);
     else
         hipLaunchKernelGGL((knn_search<KK, false>), grid, dim3(WAVE), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_search");
-    return 0;
+    return launched("knn_search");
 }
 
 int launch_cull_prep(const Params& P, hipStream_t st) {
     const int maxch = sort_chunks(P.P1 > P.P2 ? P.P1 : P.P2);
     hipLaunchKernelGGL(knn_bbox_part, dim3(NPART, P.N), dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_bbox_part");
+    if (int rc = launched("knn_bbox_part")) return rc;
     hipLaunchKernelGGL(knn_sort_pass<false>, dim3(maxch, P.N, 2), dim3(SORT_CHUNK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_sort_pass (count)");
+    if (int rc = launched("knn_sort_pass (count)")) return rc;
     hipLaunchKernelGGL(knn_col_scan, dim3(CELLS / WAVE, 2, P.N), dim3(SORT_CHUNK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_col_scan");
+    if (int rc = launched("knn_col_scan")) return rc;
     hipLaunchKernelGGL(knn_cell_scan, dim3(2, P.N), dim3(1024), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_cell_scan");
+    if (int rc = launched("knn_cell_scan")) return rc;
     hipLaunchKernelGGL(knn_sort_pass<true>, dim3(maxch, P.N, 2), dim3(SORT_CHUNK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_sort_pass (scatter)");
-    hipLaunchKernelGGL(knn_boxes, dim3((ref_chunks(P.P2) + BLOCK / WAVE - 1) / (BLOCK / WAVE), P.N), dim3(BLOCK), 0, st,
-                       P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_boxes");
-    return 0;
+    if (int rc = launched("knn_sort_pass (scatter)")) return rc;
+    hipLaunchKernelGGL(knn_boxes, dim3(ceil_div(ref_chunks(P.P2), BLOCK / WAVE), P.N), dim3(BLOCK), 0, st, P);
+    return launched("knn_boxes");
 }
 
 }  // namespace exa_knn_impl
@@ -656,12 +643,12 @@ int exa_knn_backward(int32_t N, int32_t P1, int32_t P2, int32_t K, const float* 
     P.sorted_idx = sorted_idx; P.order = order; P.g1 = grad_p1; P.g2 = grad_p2;
     hipStream_t st = (hipStream_t)stream;
     if (n1 > 0) {
-        hipLaunchKernelGGL(knn_grad_p1, dim3(blocks_for(n1)), dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_grad_p1");
+        hipLaunchKernelGGL(knn_grad_p1, dim3(ceil_div(n1, BLOCK)), dim3(BLOCK), 0, st, P);
+        if (int rc = launched("knn_grad_p1")) return rc;
     }
     if (n2 > 0) {
-        hipLaunchKernelGGL(knn_grad_p2, dim3(blocks_for(n2)), dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "knn_grad_p2");
+        hipLaunchKernelGGL(knn_grad_p2, dim3(ceil_div(n2, BLOCK)), dim3(BLOCK), 0, st, P);
+        if (int rc = launched("knn_grad_p2")) return rc;
     }
     return 0;
 }

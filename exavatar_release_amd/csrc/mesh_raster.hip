@@ -29,8 +29,12 @@
 #include <string.h>
 
 #include "../../include/exa_mesh.h"
+#include "abi_status.h"
 
 namespace exa_mesh_impl {
+
+using exa::align256;
+using exa::ceil_div;
 
 constexpr int CELL = EXA_MESH_CELL;
 constexpr int TILE = EXA_MESH_TILE;
@@ -49,7 +53,6 @@ struct alignas(16) FaceRec {
 };
 static_assert(sizeof(FaceRec) == 64, "FaceRec is 64 bytes");
 
-inline uint64_t align256(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 inline int cells_x(int W) { return (W + CELL - 1) / CELL; }
 inline int cells_y(int H) { return (H + CELL - 1) / CELL; }
 inline int words_of(int F) { return (F + 31) / 32; }
@@ -523,17 +526,7 @@ __global__ void __launch_bounds__(BLOCK) mesh_bwd_gather(Params P) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_mesh: %s", what);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_mesh: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_mesh")
 
 int check_shape(int32_t N, int32_t V, int32_t F, int32_t H, int32_t W) {
     if (N < 0 || V < 0 || F < 0 || H < 0 || W < 0) return fail(EXA_MESH_E_INVALID, "negative size");
@@ -568,17 +561,14 @@ int fill(const ExaMeshGeometry* g, const ExaMeshTexture* tex, Params& P) {
     return 0;
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 // mesh_prep + mesh_bin of a forward (nothing to do without faces)
 int launch_prep_bin(const Params& P, hipStream_t st) {
     const int64_t nf = (int64_t)P.N * P.F;
     if (nf == 0) return 0;
-    hipLaunchKernelGGL(mesh_prep, dim3(blocks_for(nf)), dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_prep");
-    hipLaunchKernelGGL(mesh_bin, dim3(blocks_for((int64_t)P.N * P.words * P.cells)), dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bin");
-    return 0;
+    hipLaunchKernelGGL(mesh_prep, dim3(ceil_div(nf, BLOCK)), dim3(BLOCK), 0, st, P);
+    if (int rc = launched("mesh_prep")) return rc;
+    hipLaunchKernelGGL(mesh_bin, dim3(ceil_div((int64_t)P.N * P.words * P.cells, BLOCK)), dim3(BLOCK), 0, st, P);
+    return launched("mesh_bin");
 }
 
 dim3 raster_grid(const Params& P) { return dim3((P.W + TILE - 1) / TILE, (P.H + TILE - 1) / TILE, P.N); }
@@ -637,8 +627,7 @@ int exa_mesh_forward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, void* 
         hipLaunchKernelGGL(mesh_raster_fwd<true>, grid, dim3(BLOCK), 0, st, P);
     else
         hipLaunchKernelGGL(mesh_raster_fwd<false>, grid, dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_raster_fwd");
-    return 0;
+    return launched("mesh_raster_fwd");
 }
 
 int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const void* face_ws,
@@ -660,16 +649,15 @@ int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const
     P.offsets = vert_offsets; P.entries = vert_entries; P.dverts = dL_dverts;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (nf > 0) {
-        const dim3 grid((unsigned)((nf + BLOCK / 64 - 1) / (BLOCK / 64)));
+        const dim3 grid(ceil_div(nf, BLOCK / 64));
         if (tex && dL_drender)
             hipLaunchKernelGGL(mesh_bwd_faces<true>, grid, dim3(BLOCK), 0, st, P);
         else
             hipLaunchKernelGGL(mesh_bwd_faces<false>, grid, dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bwd_faces");
+        if (int rc = launched("mesh_bwd_faces")) return rc;
     }
-    hipLaunchKernelGGL(mesh_bwd_gather, dim3(blocks_for(nv)), dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_bwd_gather");
-    return 0;
+    hipLaunchKernelGGL(mesh_bwd_gather, dim3(ceil_div(nv, BLOCK)), dim3(BLOCK), 0, st, P);
+    return launched("mesh_bwd_gather");
 }
 
 int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offsets, const int32_t* vert_entries,
@@ -685,10 +673,9 @@ int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offset
     P.N = g->N; P.V = g->V; P.F = g->F;
     P.verts = g->verts; P.faces = g->faces;
     P.offsets = vert_offsets; P.entries = vert_entries; P.normals_out = normals;
-    hipLaunchKernelGGL(mesh_vertex_normals, dim3(blocks_for((int64_t)P.N * P.V)), dim3(BLOCK), 0,
+    hipLaunchKernelGGL(mesh_vertex_normals, dim3(ceil_div((int64_t)P.N * P.V, BLOCK)), dim3(BLOCK), 0,
                        static_cast<hipStream_t>(stream), P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_vertex_normals");
-    return 0;
+    return launched("mesh_vertex_normals");
 }
 
 int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shading, const float* normals, void* face_ws,
@@ -710,8 +697,7 @@ int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shad
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = launch_prep_bin(P, st)) return rc;
     hipLaunchKernelGGL((mesh_raster_fwd<false, true>), raster_grid(P), dim3(BLOCK), 0, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mesh_raster_fwd (shaded)");
-    return 0;
+    return launched("mesh_raster_fwd (shaded)");
 }
 
 }  // extern "C"

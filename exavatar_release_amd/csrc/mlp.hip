@@ -27,8 +27,11 @@
 #include <string.h>
 
 #include "../../include/exa_mlp.h"
+#include "abi_status.h"
 
 namespace exa_mlp_impl {
+
+using exa::ceil_div;
 
 constexpr int H = EXA_MLP_HIDDEN;
 constexpr int MAXL = EXA_MLP_MAX_LAYERS;
@@ -569,17 +572,7 @@ __global__ void __launch_bounds__(BLOCK) mlp_bwd_sum(Params P) {
     }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_mlp: %s", what);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_mlp: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_mlp")
 
 int check_net(const exa_mlp_net* n, int* nh_out) {
     if (!n) return fail(EXA_MLP_E_NULLPTR, "net is NULL");
@@ -695,10 +688,8 @@ int exa_mlp_forward(const exa_mlp_net* net, int32_t N, const float* x, float* co
     }
     P.x = x;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)(((int64_t)N + ROWS - 1) / ROWS));
-    EXA_MLP_DISPATCH(mlp_fwd, grid, 0)
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "mlp_fwd");
-    return 0;
+    EXA_MLP_DISPATCH(mlp_fwd, dim3(ceil_div(N, ROWS)), 0)
+    return launched("mlp_fwd");
 }
 
 int exa_mlp_backward(const exa_mlp_net* net, int32_t N, const float* x, const float* const* grad_out, float* grad_x,
@@ -724,19 +715,18 @@ int exa_mlp_backward(const exa_mlp_net* net, int32_t N, const float* x, const fl
     hipStream_t st = (hipStream_t)stream;
     const bool params = grad_params || P.gws;
     if (N > 0 && (grad_x || params)) {
-        const dim3 grid((unsigned)(((int64_t)N + ROWS - 1) / ROWS));
-        EXA_MLP_DISPATCH(mlp_bwd_rows, grid, 0)
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "mlp_bwd_rows");
+        EXA_MLP_DISPATCH(mlp_bwd_rows, dim3(ceil_div(N, ROWS)), 0)
+        if (int rc = launched("mlp_bwd_rows")) return rc;
         if (params) {
             const dim3 g2((unsigned)P.nchunks, (unsigned)(net->n_layers + 1));
             EXA_MLP_DISPATCH(mlp_bwd_chunk, g2, 0)
-            if (hipError_t e = hipGetLastError()) return fail_hip(e, "mlp_bwd_chunk");
+            if (int rc = launched("mlp_bwd_chunk")) return rc;
         }
     }
     if (params) {
         const int64_t tot = P.P + (int64_t)H * net->shared_width;
-        hipLaunchKernelGGL(mlp_bwd_sum, dim3((unsigned)((tot + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "mlp_bwd_sum");
+        hipLaunchKernelGGL(mlp_bwd_sum, dim3(ceil_div(tot, BLOCK)), dim3(BLOCK), 0, st, P);
+        if (int rc = launched("mlp_bwd_sum")) return rc;
     }
     return 0;
 }

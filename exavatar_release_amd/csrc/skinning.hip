@@ -23,8 +23,11 @@
 #include <string.h>
 
 #include "../../include/exa_skin.h"
+#include "abi_status.h"
 
 namespace exa_skin_impl {
+
+using exa::ceil_div;
 
 constexpr int MAXJ = EXA_SKIN_MAX_JOINTS;
 constexpr int MAXS = EXA_SKIN_MAX_SETS;
@@ -315,17 +318,7 @@ __global__ __launch_bounds__(SUM_BLOCK) void skin_bwd_sum(SumParams P) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_skin: %s", what);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_skin: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_skin")
 
 int check_shape(int32_t V, int32_t S, int32_t J, int32_t Vw, const int64_t* idx) {
     if (V < 0) return fail(EXA_SKIN_E_INVALID, "negative vertex count V");
@@ -390,9 +383,8 @@ int exa_skin_forward(int32_t V, int32_t S, int32_t J, int32_t Vw, const float* c
     if (int rc = copy_sets(out, S, P.out, "out (or one of its S entries) is NULL")) return rc;
     P.trans = trans;
     P.t = t;
-    hipLaunchKernelGGL(skin_fwd, dim3((unsigned)(((int64_t)V + SUB - 1) / SUB)), dim3(SUB), 0, (hipStream_t)stream, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "skin_fwd");
-    return 0;
+    hipLaunchKernelGGL(skin_fwd, dim3(ceil_div(V, SUB)), dim3(SUB), 0, (hipStream_t)stream, P);
+    return launched("skin_fwd");
 }
 
 int exa_skin_backward(int32_t V, int32_t S, int32_t J, int32_t Vw, const float* const* points, const float* weights,
@@ -413,12 +405,11 @@ int exa_skin_backward(int32_t V, int32_t S, int32_t J, int32_t Vw, const float* 
         P.partials = (float*)workspace;
         Q.partials = P.partials;
         hipLaunchKernelGGL(skin_bwd_chunk, dim3((unsigned)num_chunks(V)), dim3(BWD_BLOCK), 0, st, P);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "skin_bwd_chunk");
+        if (int rc = launched("skin_bwd_chunk")) return rc;
     }
     if (!grad_T && !grad_trans) return 0;
-    hipLaunchKernelGGL(skin_bwd_sum, dim3((unsigned)((16 * J + 3 + SUM_COLS - 1) / SUM_COLS)), dim3(SUM_BLOCK), 0, st, Q);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "skin_bwd_sum");
-    return 0;
+    hipLaunchKernelGGL(skin_bwd_sum, dim3(ceil_div(16 * J + 3, SUM_COLS)), dim3(SUM_BLOCK), 0, st, Q);
+    return launched("skin_bwd_sum");
 }
 
 }  // extern "C"

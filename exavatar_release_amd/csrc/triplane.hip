@@ -24,8 +24,11 @@
 #include <string.h>
 
 #include "../../include/exa_triplane.h"
+#include "abi_status.h"
 
 namespace exa_triplane_impl {
+
+using exa::ceil_div;
 
 constexpr int FWD_BLOCK = 256;
 constexpr int BWD_BLOCK = 1024;
@@ -217,17 +220,7 @@ __global__ __launch_bounds__(BWD_BLOCK) void triplane_bwd(BwdParams P) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what) {
-    snprintf(g_err, sizeof(g_err), "exa_triplane: %s", what);
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* where) {
-    snprintf(g_err, sizeof(g_err), "exa_triplane: HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), where);
-    return (int)e;
-}
+EXA_ABI_STATUS("exa_triplane")
 
 int check_shape(int32_t N, int32_t C, int32_t H, int32_t W) {
     if (N < 0) return fail(EXA_TRIPLANE_E_INVALID, "negative row count");
@@ -239,8 +232,6 @@ int check_shape(int32_t N, int32_t C, int32_t H, int32_t W) {
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-unsigned blocks(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 }  // namespace exa_triplane_impl
 
@@ -258,10 +249,9 @@ int exa_triplane_plan_keys(int32_t N, int32_t H, int32_t W, const float* coords,
     if (N == 0) return 0;
     if (!coords || !is_face || !keys) return fail(EXA_TRIPLANE_E_NULLPTR, "coords / is_face / keys is NULL");
     KeyParams P = {N, H, W, coords, is_face, keys};
-    hipLaunchKernelGGL(triplane_plan_keys, dim3(blocks((int64_t)N * 3, KEY_BLOCK)), dim3(KEY_BLOCK), 0,
+    hipLaunchKernelGGL(triplane_plan_keys, dim3(ceil_div((int64_t)N * 3, KEY_BLOCK)), dim3(KEY_BLOCK), 0,
                        (hipStream_t)stream, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "triplane_plan_keys");
-    return 0;
+    return launched("triplane_plan_keys");
 }
 
 int exa_triplane_forward(int32_t N, int32_t C, int32_t H, int32_t W, const float* body, const float* face,
@@ -273,13 +263,12 @@ int exa_triplane_forward(int32_t N, int32_t C, int32_t H, int32_t W, const float
     FwdParams P = {N, C, H, W, body, face, coords, is_face, out};
     hipStream_t st = (hipStream_t)stream;
     if (C % 4 == 0 && aligned16(out)) {
-        hipLaunchKernelGGL(triplane_fwd<4>, dim3(blocks((int64_t)N * 3 * (C / 4), FWD_BLOCK)), dim3(FWD_BLOCK), 0, st,
-                           P);
+        hipLaunchKernelGGL(triplane_fwd<4>, dim3(ceil_div((int64_t)N * 3 * (C / 4), FWD_BLOCK)), dim3(FWD_BLOCK), 0,
+                           st, P);
     } else {
-        hipLaunchKernelGGL(triplane_fwd<1>, dim3(blocks((int64_t)N * 3 * C, FWD_BLOCK)), dim3(FWD_BLOCK), 0, st, P);
+        hipLaunchKernelGGL(triplane_fwd<1>, dim3(ceil_div((int64_t)N * 3 * C, FWD_BLOCK)), dim3(FWD_BLOCK), 0, st, P);
     }
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "triplane_fwd");
-    return 0;
+    return launched("triplane_fwd");
 }
 
 int exa_triplane_backward(int32_t N, int32_t C, int32_t H, int32_t W, const float* coords, const float* grad_out,
@@ -302,8 +291,7 @@ int exa_triplane_backward(int32_t N, int32_t C, int32_t H, int32_t W, const floa
         hipLaunchKernelGGL(triplane_bwd<4>, dim3(num_wg), dim3(BWD_BLOCK), lds, st, P);
     else
         hipLaunchKernelGGL(triplane_bwd<1>, dim3(num_wg), dim3(BWD_BLOCK), lds, st, P);
-    if (hipError_t e = hipGetLastError()) return fail_hip(e, "triplane_bwd");
-    return 0;
+    return launched("triplane_bwd");
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ in a multi-GPU run the statistics are then combined with ``dist.reduce_densify_s
 import torch
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr
+from ._device import _ptr, _stream_ptr
 
 
 def track_densify_stats(mean_2d_grad, radius, xyz_grad_accum=None, track_cnt=None, radius_max=None):

@@ -26,22 +26,16 @@ Gradients: ``dists`` and ``knn`` are differentiable with respect to both point s
 (``exa_knn_backward``), which sums every output element in a fixed order without atomics, so the gradients are
 bit-reproducible; the stable ordering of ``idx`` it takes as input is a ``torch.sort(stable=True)``.
 """
-import ctypes
 from collections import namedtuple
 
 import torch
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr, _workspace, config
+from ._device import _ptr, _stream_ptr, _workspace, config, need_rocm
 
 KNN = namedtuple('KNN', 'dists idx knn')
 
 MAX_K = 32
-
-
-def _need_rocm(device, what):
-    if device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
 
 
 class _KnnPoints(torch.autograd.Function):
@@ -59,7 +53,7 @@ class _KnnPoints(torch.autograd.Function):
             nbytes = _lib.knn_workspace_size(N, P1, P2, K) if config.knn_cull else 0
             ws = _workspace(nbytes, device)
             with torch.cuda.device(device):
-                _lib.check_knn(_lib.load().exa_knn_forward(N, P1, P2, K, _ptr(p1), _ptr(p2), flags, _ptr(ws), nbytes,
+                _lib.KNN.check(_lib.load().exa_knn_forward(N, P1, P2, K, _ptr(p1), _ptr(p2), flags, _ptr(ws), nbytes,
                                                            _ptr(dists), _ptr(idx), None, _stream_ptr(device)))
         if want_nn:
             knn = torch.gather(p2, 1, idx.view(N, P1 * K, 1).expand(N, P1 * K, 3)).view(N, P1, K, 3)
@@ -87,7 +81,7 @@ class _KnnPoints(torch.autograd.Function):
         if N * (P1 + P2) > 0:
             sorted_idx, order = torch.sort(idx.view(N, P1 * K), dim=1, stable=True)
             with torch.cuda.device(p1.device):
-                _lib.check_knn(_lib.load().exa_knn_backward(N, P1, P2, K, _ptr(p1), _ptr(p2), _ptr(idx),
+                _lib.KNN.check(_lib.load().exa_knn_backward(N, P1, P2, K, _ptr(p1), _ptr(p2), _ptr(idx),
                                                             _ptr(grad_dists), _ptr(grad_knn), _ptr(sorted_idx),
                                                             _ptr(order), _ptr(grad_p1), _ptr(grad_p2),
                                                             _stream_ptr(p1.device)))
@@ -109,8 +103,8 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
         raise NotImplementedError('knn_points: D = 3 only')
     if not 1 <= int(K) <= MAX_K:
         raise ValueError('knn_points: K must be 1 .. %d' % MAX_K)
-    _need_rocm(p1.device, 'knn_points')
-    _need_rocm(p2.device, 'knn_points')
+    need_rocm(p1.device, 'knn_points')
+    need_rocm(p2.device, 'knn_points')
     if p1.device != p2.device:
         raise ValueError('knn_points: p1 and p2 are on different devices')
     if p1.dtype != torch.float32 or p2.dtype != torch.float32:

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr
+from ._device import _ptr, _stream_ptr, need_rocm
 
 
 def _crop_window(bbox, img_height, img_width):
@@ -46,17 +46,12 @@ def _dev_f32(t, device, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _need_rocm(device, what):
-    if device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
-
-
 class _L1Map(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img_out, img_target, mask, bg, crop):
         lib = _lib.load()
         device = img_out.device
-        _need_rocm(device, 'RGBLoss')
+        need_rocm(device, 'RGBLoss')
         if img_out.dim() != 4 or img_out.shape != img_target.shape:
             raise ValueError('RGBLoss expects two [B, C, H, W] images of the same shape')
         x, y = _dev_f32(img_out, device, 'img_out'), _dev_f32(img_target, device, 'img_target')
@@ -107,7 +102,7 @@ class _FusedSSIM(torch.autograd.Function):
     def forward(ctx, img_out, img_target):
         lib = _lib.load()
         device = img_out.device
-        _need_rocm(device, 'the fused SSIM')
+        need_rocm(device, 'the fused SSIM')
         x = img_out.detach().to(torch.float32).contiguous()
         y = img_target.detach().to(device=device, dtype=torch.float32).contiguous()
         if x.dim() != 4 or x.shape != y.shape:
@@ -172,7 +167,7 @@ class _Photometric(torch.autograd.Function):
     def forward(ctx, img_out, img_target, l1_weight, ssim_mask, crop, w_l1, w_ssim):
         lib = _lib.load()
         device = img_out.device
-        _need_rocm(device, 'PhotometricLoss')
+        need_rocm(device, 'PhotometricLoss')
         if img_out.dim() != 4 or img_out.shape != img_target.shape:
             raise ValueError('PhotometricLoss expects two [B, C, H, W] images of the same shape')
         x, y = _dev_f32(img_out, device, 'img_out'), _dev_f32(img_target, device, 'img_target')

@@ -79,7 +79,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr
+from ._device import _ptr, _stream_ptr, need_rocm
 
 Fragments = collections.namedtuple('Fragments', ['pix_to_face', 'zbuf', 'bary_coords', 'dists'])
 Fragments.__doc__ = """pytorch3d ``Fragments`` of one face per pixel: ``pix_to_face`` [N,H,W,1] int64 (packed n * F + f, -1 for
@@ -100,7 +100,7 @@ def _topology(face, V, device):
     F = host.shape[0]
     offsets = np.zeros(V + 1, dtype=np.int32)
     entries = np.zeros(max(3 * F, 1), dtype=np.int32)
-    _lib.check_mesh(_lib.load().exa_mesh_vertex_faces(V, F, host.ctypes.data, offsets.ctypes.data, entries.ctypes.data))
+    _lib.MESH.check(_lib.load().exa_mesh_vertex_faces(V, F, host.ctypes.data, offsets.ctypes.data, entries.ctypes.data))
     entry = (host, torch.from_numpy(host).to(device), torch.from_numpy(offsets).to(device),
              torch.from_numpy(entries).to(device))
     if len(_topologies) > 16:
@@ -144,7 +144,7 @@ def _forward(verts, topo, focal, princpt, H, W, texture, face_uvs, want_zbary):
     g = _geometry(verts, faces, focal, princpt, H, W)
     t = _texture(texture, face_uvs)
     with torch.cuda.device(device):
-        _lib.check_mesh(lib.exa_mesh_forward(ctypes.byref(g), ctypes.byref(t) if t is not None else None,
+        _lib.MESH.check(lib.exa_mesh_forward(ctypes.byref(g), ctypes.byref(t) if t is not None else None,
                                              _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), _ptr(zbuf), _ptr(bary),
                                              _ptr(render), _stream_ptr(device)))
     return face_ws, pix_to_face, zbuf, bary, render
@@ -165,15 +165,10 @@ def _backward(ctx, dzbuf, dbary, drender):
     f32 = lambda x: None if x is None else x.to(torch.float32).contiguous()      # noqa: E731
     dzbuf, dbary, drender = f32(dzbuf), f32(dbary), f32(drender)
     with torch.cuda.device(device):
-        _lib.check_mesh(lib.exa_mesh_backward(ctypes.byref(g), ctypes.byref(t) if t is not None else None, _ptr(face_ws),
+        _lib.MESH.check(lib.exa_mesh_backward(ctypes.byref(g), ctypes.byref(t) if t is not None else None, _ptr(face_ws),
                                               _ptr(pix_to_face), _ptr(dzbuf), _ptr(dbary), _ptr(drender), _ptr(offsets),
                                               _ptr(entries), _ptr(grad_ws), _ptr(dverts), _stream_ptr(device)))
     return dverts
-
-
-def _need_rocm(device, what):
-    if device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
 
 
 class _RasterizeMesh(torch.autograd.Function):
@@ -217,7 +212,7 @@ class _RenderMesh(torch.autograd.Function):
 def _check_mesh(mesh, what):
     if not isinstance(mesh, torch.Tensor) or mesh.dim() != 3 or mesh.shape[2] != 3:
         raise ValueError('%s: mesh must be a [N, V, 3] tensor' % what)
-    _need_rocm(mesh.device, what)
+    need_rocm(mesh.device, what)
 
 
 def get_face_index_map_xy(mesh, face, cam_param, render_shape):
@@ -280,7 +275,7 @@ def _vertex_normals(verts, topo):
     g = _lib.ExaMeshGeometry(verts.shape[0], verts.shape[1], faces.shape[0], 0, 0, verts.data_ptr(), faces.data_ptr(),
                              None, None)
     with torch.cuda.device(verts.device):
-        _lib.check_mesh(_lib.load().exa_mesh_vertex_normals(ctypes.byref(g), _ptr(offsets), _ptr(entries), _ptr(normals),
+        _lib.MESH.check(_lib.load().exa_mesh_vertex_normals(ctypes.byref(g), _ptr(offsets), _ptr(entries), _ptr(normals),
                                                             _stream_ptr(verts.device)))
     return normals
 
@@ -350,7 +345,7 @@ def shade_mesh(mesh, face, cam_param, render_shape, *, light_location=(0.0, -1.0
     pix_to_face = torch.empty((N, H, W), dtype=torch.int64, device=device)
     g = _geometry(verts, faces, focal, princpt, H, W)
     with torch.cuda.device(device):
-        _lib.check_mesh(_lib.load().exa_mesh_forward_shaded(ctypes.byref(g), ctypes.byref(sh), _ptr(normals),
+        _lib.MESH.check(_lib.load().exa_mesh_forward_shaded(ctypes.byref(g), ctypes.byref(sh), _ptr(normals),
                                                             _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), None,
                                                             _ptr(image), _stream_ptr(device)))
     return image, pix_to_face

@@ -23,7 +23,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .rasterizer import _stream_ptr, _workspace
+from ._device import _stream_ptr, _workspace
+from ._lib import ExaMlpNet
 
 HIDDEN = 128              # EXA_MLP_HIDDEN
 MAX_LAYERS = 4            # EXA_MLP_MAX_LAYERS
@@ -33,15 +34,6 @@ MAX_HEADS = 4             # EXA_MLP_MAX_HEADS
 MAX_OUT = 32              # EXA_MLP_MAX_OUT
 CHUNK = 512               # EXA_MLP_CHUNK
 GROUPS = (1, 2, 4)
-
-
-class ExaMlpNet(ctypes.Structure):
-    _fields_ = [('n_layers', ctypes.c_int32), ('in_width', ctypes.c_int32), ('shared_width', ctypes.c_int32),
-                ('groups', ctypes.c_int32), ('n_heads', ctypes.c_int32), ('head_width', ctypes.c_int32 * MAX_HEADS),
-                ('ld_w0', ctypes.c_int32), ('ld_ws', ctypes.c_int32), ('eps', ctypes.c_float * MAX_LAYERS),
-                ('W', ctypes.c_void_p * MAX_LAYERS), ('b', ctypes.c_void_p * MAX_LAYERS),
-                ('gamma', ctypes.c_void_p * MAX_LAYERS), ('beta', ctypes.c_void_p * MAX_LAYERS),
-                ('Ws', ctypes.c_void_p), ('shared', ctypes.c_void_p), ('Wh', ctypes.c_void_p), ('bh', ctypes.c_void_p)]
 
 
 def parse_structure(trunk, heads=None):
@@ -137,7 +129,7 @@ class _MLP(torch.autograd.Function):
         net = _net(layers, hs, K0, S, W0, Ws, p, Wh, bh, trunk)
         outs = [torch.empty((N, hd.out_features), dtype=torch.float32, device=dev) for hd in hs]
         with torch.cuda.device(dev):
-            _lib.check_mlp(_lib.load().exa_mlp_forward(ctypes.byref(net), N, x.data_ptr() if N else None,
+            _lib.MLP.check(_lib.load().exa_mlp_forward(ctypes.byref(net), N, x.data_ptr() if N else None,
                                                        (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs]),
                                                        _stream_ptr(dev)))
         ctx.meta = meta
@@ -161,16 +153,16 @@ class _MLP(torch.autograd.Function):
         gx = torch.empty((N, K0), dtype=torch.float32, device=dev) if need[1] else None
         want_params = need[3] or need[5] or need[6] or any(need[7:])
         count = ctypes.c_int64()
-        _lib.check_mlp(_lib.load().exa_mlp_param_count(ctypes.byref(net), ctypes.byref(count)))
+        _lib.MLP.check(_lib.load().exa_mlp_param_count(ctypes.byref(net), ctypes.byref(count)))
         gp = torch.empty(int(count.value), dtype=torch.float32, device=dev) if want_params else None
         gws = torch.empty((HIDDEN, S), dtype=torch.float32, device=dev) if (S and need[4]) else None
         nbytes = ctypes.c_uint64()
-        _lib.check_mlp(_lib.load().exa_mlp_workspace_size(ctypes.byref(net), N, ctypes.byref(nbytes)))
+        _lib.MLP.check(_lib.load().exa_mlp_workspace_size(ctypes.byref(net), N, ctypes.byref(nbytes)))
         nbytes = int(nbytes.value)
         ws = _workspace(nbytes, dev) if nbytes and (gx is not None or gp is not None or gws is not None) else None
         if gx is not None or gp is not None or gws is not None:
             with torch.cuda.device(dev):
-                _lib.check_mlp(_lib.load().exa_mlp_backward(
+                _lib.MLP.check(_lib.load().exa_mlp_backward(
                     ctypes.byref(net), N, x.data_ptr() if N else None,
                     (ctypes.c_void_p * len(gouts))(*[g.data_ptr() if g is not None else None for g in gouts]),
                     gx.data_ptr() if gx is not None and N else None, gp.data_ptr() if gp is not None else None,

@@ -55,6 +55,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._device import _addr, _ptr, _stream_ptr, _workspace, config
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -71,34 +72,6 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool          # accepted and ignored (include/exa_raster.h): the library always culls itself
     debug: bool
 
-
-class _Config:
-    mode = 'auto'             # 'auto' | 'exact' | 'capacity'
-    capacity_growth = 1.5     # capacity mode: head-room over the largest D seen so far
-    min_capacity = 1 << 16
-    fixed_capacity = None     # capacity mode: use exactly this many instances (e.g. calibrated by a warm-up); a list /
-    #                           tuple names one capacity per job of a batched call
-    keep_debug = False        # developer probes: keep the workspaces of the most recent forward reachable
-    on_overflow = 'retry'     # 'retry' | 'raise' (module docstring)
-    overlap_composites = True     # INSIDE a stream capture: the composites' list merges run on a second stream while their sources
-    #                               blend (the calls are split at EXA_RASTER_STAGE_NO_BLEND; fork / join become graph edges).
-    #                               Eager calls never do this: the stream switches cost the host more than the overlap gives
-    fold_composite_grads = True   # a composite's gradients for source B are handed to B's own render, whose backward adds them
-    #                               inside its per-Gaussian kernel (ExaRasterBackwardJob.accumulate) instead of autograd
-    #                               summing the two with one kernel per tensor (developer A/B knob; same values bit for bit)
-    compose_reuse_source = True   # composite renders copy source A's pixels where source B has no entry (developer A/B knob)
-    upstream_scale_grad = False   # True: dL/dscale as upstream returns it (w.r.t. scale_modifier * scale, i.e. divided
-    #                               by scale_modifier); identical for the reference, which passes 1.0 (module.py:615)
-    knn_cull = True               # knn_points: cull ref chunks by their boxes (False: visit every ref; the same bits either way)
-    poison = False                # debug: fill every workspace with 0xFF before the kernels see it (the library promises to write
-    #                               every section before it reads it; tests run under it with EXA_TEST_POISON=1)
-    compiled_node = 'auto'        # single renders through the compiled autograd node (csrc/torch_binding.cpp -> _exa_torch.so: the
-    #                               same C-ABI calls, arena layouts and overflow protocol as _Rasterize below at a quarter of the
-    #                               host time): 'auto' = when it is built and the call is one it covers, 'off' = always the Python
-    #                               node, 'require' = raise if the extension is missing
-
-
-config = _Config()
 
 _debug_last = {}  # only filled when config.keep_debug (tools/): workspaces of the most recent forward
 _seen_D = {}      # (device index, P, H, W) -> largest instance capacity a call of that shape needed
@@ -126,23 +99,6 @@ def take_is_vis():
     return v
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _workspace(nbytes, device):
-    """Uninitialised byte workspace (``config.poison``: filled with 0xFF, so that a kernel reading a section nobody
-    wrote sees the worst garbage instead of whatever the allocator left there)."""
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    if config.poison:
-        ws.fill_(255)
-    return ws
-
-
-def _addr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _f32c(t, name, device, memo=None):
     """float32, contiguous, on ``device``.  ``memo`` (id -> converted tensor) makes K jobs that pass the SAME tensor
     object share one converted copy -- so that a batch of K views of one model still presents identical pointers to
@@ -165,10 +121,6 @@ def _f32c(t, name, device, memo=None):
     if memo is not None:
         memo[id(t)] = (t, c)
     return c
-
-
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _NoCtx:

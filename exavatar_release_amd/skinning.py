@@ -28,25 +28,13 @@ Each call allocates its outputs (and, backward, a workspace from the torch alloc
 two backward; the kernels do not synchronise and can be captured into a hipGraph.  The camera step's ``torch.inverse(R)``
 is torch's and synchronises on ROCm, so a call with ``R`` cannot be captured; one without can.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr, _workspace
+from ._device import _ptr, _ptrs, _stream_ptr, _workspace, need_rocm
 
 MAX_JOINTS = 64           # EXA_SKIN_MAX_JOINTS
 MAX_SETS = 4              # EXA_SKIN_MAX_SETS
-
-
-def _need_rocm(device, what):
-    if device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
-
-
-def _ptrs(tensors):
-    """Host array of device pointers (NULL for None)."""
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
 class _Skin(torch.autograd.Function):
@@ -59,7 +47,7 @@ class _Skin(torch.autograd.Function):
         dev = T.device
         outs = [torch.empty((V, 3), dtype=torch.float32, device=dev) for _ in points]
         with torch.cuda.device(dev):
-            _lib.check_skin(_lib.load().exa_skin_forward(V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T),
+            _lib.SKIN.check(_lib.load().exa_skin_forward(V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T),
                                                          _ptr(trans), _ptr(Rinv), _ptr(t), _ptrs(outs),
                                                          _stream_ptr(dev)))
         ctx.has_idx = idx is not None
@@ -85,7 +73,7 @@ class _Skin(torch.autograd.Function):
             nbytes = _lib.skin_workspace_size(V, J)
             ws = _workspace(nbytes, dev)
             with torch.cuda.device(dev):
-                _lib.check_skin(_lib.load().exa_skin_backward(
+                _lib.SKIN.check(_lib.load().exa_skin_backward(
                     V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T), _ptr(Rinv), _ptrs(grads),
                     _ptrs(gpts), _ptr(gT), _ptr(gtrans), _ptr(ws) if nbytes else None, nbytes, _stream_ptr(dev)))
         return (None, None, None, None, gT, gtrans) + tuple(gpts)
@@ -148,7 +136,7 @@ def skin_points(points, transform_mat_joint, skinning_weight, idx=None, trans=No
                     ('R', R), ('t', t)] + [('points[%d]' % s, x) for s, x in enumerate(sets)]:
         if x is None:
             continue
-        _need_rocm(x.device, 'skin_points')
+        need_rocm(x.device, 'skin_points')
         if x.device != dev:
             raise ValueError('skin_points: %s is not on the device of transform_mat_joint' % name)
     if trans is None:

@@ -37,12 +37,9 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rz
+from ._device import _addr
 
 _F32 = torch.float32
-
-
-def _addr(t):
-    return None if t is None else t.data_ptr()
 
 
 def required_capacity(means3D, opacities, scales, rotations, colors_precomp=None, shs=None, *, settings):

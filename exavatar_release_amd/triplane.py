@@ -29,16 +29,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _ptr, _stream_ptr
+from ._device import _ptr, _stream_ptr, need_rocm
 
 BWD_BLOCK = 1024          # threads of a backward workgroup (csrc/triplane.hip)
 MAX_LDS = 65536           # EXA_TRIPLANE_MAX_LDS
 MIN_SEG_LEN = 32
-
-
-def _need_rocm(device, what):
-    if device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
 
 
 def normalize_coords(pos_enc_mesh, is_face, shape_3d=(2, 2, 2), face_shape_3d=(0.3, 0.3, 0.3)):
@@ -113,7 +108,7 @@ class _Plan:
         keys = torch.empty(N * 12, dtype=torch.int32, device=dev)
         if N:
             with torch.cuda.device(dev):
-                _lib.check_triplane(_lib.load().exa_triplane_plan_keys(N, H, W, _ptr(coords), _ptr(is_face_u8),
+                _lib.TRIPLANE.check(_lib.load().exa_triplane_plan_keys(N, H, W, _ptr(coords), _ptr(is_face_u8),
                                                                        _ptr(keys), _stream_ptr(dev)))
         self.keys = keys
         for k, v in plan_tables(keys, 6 * H * W, C).items():
@@ -130,7 +125,7 @@ class _TriplaneLookup(torch.autograd.Function):
         out = torch.empty((N, 3 * C), dtype=torch.float32, device=body.device)
         if N:
             with torch.cuda.device(body.device):
-                _lib.check_triplane(_lib.load().exa_triplane_forward(N, C, H, W, _ptr(body), _ptr(face), _ptr(tf.coords),
+                _lib.TRIPLANE.check(_lib.load().exa_triplane_forward(N, C, H, W, _ptr(body), _ptr(face), _ptr(tf.coords),
                                                                      _ptr(tf.is_face_u8), _ptr(out),
                                                                      _stream_ptr(body.device)))
         ctx.tf = tf
@@ -146,7 +141,7 @@ class _TriplaneLookup(torch.autograd.Function):
         grad_body = torch.empty((3, C, H, W), dtype=torch.float32, device=dev)
         grad_face = torch.empty((3, C, H, W), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check_triplane(_lib.load().exa_triplane_backward(
+            _lib.TRIPLANE.check(_lib.load().exa_triplane_backward(
                 tf.num_rows, C, H, W, _ptr(tf.coords), _ptr(grad_out), _ptr(p.entries), _ptr(p.seg_entry),
                 _ptr(p.tex_seg), _ptr(p.wg_tex), p.num_wg, p.max_wg_segments, _ptr(grad_body), _ptr(grad_face),
                 _stream_ptr(dev)))
@@ -173,8 +168,8 @@ class TriplaneFeatures:
         C, H, W = (int(s) for s in triplane_shape)
         if not (1 <= C <= 1024 and H >= 1 and W >= 1):
             raise ValueError('TriplaneFeatures: triplane_shape must be (C, H, W) with 1 <= C <= 1024, H, W >= 1')
-        _need_rocm(pos_enc_mesh.device, 'TriplaneFeatures')
-        _need_rocm(is_face.device, 'TriplaneFeatures')
+        need_rocm(pos_enc_mesh.device, 'TriplaneFeatures')
+        need_rocm(is_face.device, 'TriplaneFeatures')
         if pos_enc_mesh.device != is_face.device:
             raise ValueError('TriplaneFeatures: pos_enc_mesh and is_face are on different devices')
         self.triplane_shape = (C, H, W)
@@ -188,7 +183,7 @@ class TriplaneFeatures:
     def _check_planes(self, triplane, triplane_face):
         want = (3,) + self.triplane_shape
         for name, t in (('triplane', triplane), ('triplane_face', triplane_face)):
-            _need_rocm(t.device, 'TriplaneFeatures')
+            need_rocm(t.device, 'TriplaneFeatures')
             if t.device != self.device:
                 raise ValueError('TriplaneFeatures: %s is not on the device of the coordinates' % name)
             if t.dtype != torch.float32:

@@ -1,6 +1,6 @@
-"""CPU tests of the host side: the C-ABI library loads and exports every declared symbol, argument
-validation works without a GPU, the Python surface mirrors the reference's plugin interface, and the
-product path refuses to run without a ROCm device (no CPU fallback)."""
+"""CPU tests of the host side: argument validation works without a GPU, the Python surface mirrors the
+reference's plugin interface, and the product path refuses to run without a ROCm device (no CPU fallback).
+The C ABI itself (include/exa_raster.h against its binding) is checked by tests/test_abi.py."""
 import ctypes
 import os
 import re
@@ -12,29 +12,6 @@ import exavatar_release_amd as exa
 from exavatar_release_amd import _lib, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_functions():
-    src = open(os.path.join(ROOT, 'include', 'exa_raster.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(exa_(?:raster|ssim|photo|l1)_\w+)\s*\(', src)))
-
-
-def test_library_exports_every_symbol_the_header_declares():
-    lib = _lib.load()
-    names = _declared_functions()
-    assert len(names) >= 24
-    for n in names:
-        assert hasattr(lib, n), n
-        assert n in _lib.SIGNATURES, 'ctypes signature missing for ' + n
-    assert lib.exa_raster_version() == 139
-    assert [lib.exa_raster_timing_name(i) for i in range(_lib.TIMING_SLOTS)][1] == b'preprocess_fwd'
-
-
-def test_settings_struct_layout_matches_c():
-    # 4 ints/floats, ptr, float(+pad), 2 ptrs, int(+pad), ptr, 2 ints  on LP64
-    assert ctypes.sizeof(_lib.ExaRasterSettings) == 72
-    assert _lib.ExaRasterSettings.bg.offset == 16 and _lib.ExaRasterSettings.campos.offset == 56
 
 
 def test_workspace_sizes():
@@ -322,36 +299,6 @@ def test_static_render_rejects_what_it_cannot_drive():
     with pytest.raises(ValueError, match='on a GPU'):
         exa.StaticRender(z(P, 3), z(P, 1), z(P, 3), z(P, 4), colors_precomp=z(P, 3), image_size=(16, 16), capacity=64)
     assert 'StaticRender' in exa.__all__ and 'required_capacity' in exa.__all__
-
-
-def test_header_compiles_as_plain_c_and_cxx_and_links_against_the_library(tmp_path):
-    """include/exa_raster.h is the drop-in boundary for NATIVE hosts: it has to compile as C99 and as C++11
-    without torch, HIP or any other header of ours, and a C program that takes the address of every function it declares
-    has to link against libexa_raster.so (no compute call: there is no GPU here)."""
-    import shutil
-    import subprocess
-    if shutil.which('gcc') is None:
-        pytest.skip('no gcc')
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, 'include', 'exa_raster.h')).read()
-    names = sorted(set(re.findall(r'\b(exa_(?:raster|l1|photo|ssim)_\w+)\s*\(', hdr)))
-    assert set(names) == set(_lib.SIGNATURES), 'binding and header disagree on the exported functions'
-    src = tmp_path / 'host.c'
-    src.write_text('#include "exa_raster.h"\n#include <stdio.h>\nint main(void) {\n  void* f[] = {%s};\n'
-                   '  ExaRasterForwardJob fj; ExaRasterBackwardJob bj; ExaRasterComposeJob cj; (void)fj; (void)bj; (void)cj;\n'
-                   '  printf("%%d %%d\\n", (int)(sizeof f / sizeof f[0]), exa_raster_version());\n  return 0;\n}\n'
-                   % ', '.join('(void*)' + n for n in names))
-    inc = ['-I', os.path.join(root, 'include')]
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-Wno-pedantic', '-fsyntax-only'] + inc + [str(src)], check=True)
-    if shutil.which('g++'):
-        subprocess.run(['g++', '-std=c++11', '-Wall', '-Wextra', '-Werror', '-fsyntax-only', '-x', 'c++'] + inc + [str(src)], check=True)
-    lib = os.path.join(root, 'exavatar_release_amd', 'libexa_raster.so')
-    exe = tmp_path / 'host'
-    subprocess.run(['gcc', '-std=c99'] + inc + [str(src), lib, '-Wl,-rpath,' + os.path.dirname(lib), '-Wl,--allow-shlib-undefined',
-                                                 '-o', str(exe)], check=True)
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''))
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, env=env).stdout.split()
-    assert int(out[0]) == len(names) and int(out[1]) == _lib.load().exa_raster_version()
 
 
 def test_native_host_example_compiles_and_links(tmp_path):

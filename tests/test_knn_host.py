@@ -1,9 +1,7 @@
-"""CPU tests of the knn_points host side: every exa_knn_* function of include/exa_knn.h is exported and bound, invalid
-arguments fail with a negative status before any GPU work, and the Python surface refuses CPU tensors and the
-unsupported options."""
+"""CPU tests of the knn_points host side: invalid arguments fail with a negative status before any GPU work, and the
+Python surface refuses CPU tensors and the unsupported options.  The ABI itself (include/exa_knn.h against its binding)
+is checked by tests/test_abi.py."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -11,25 +9,7 @@ import torch
 import exavatar_release_amd as exa
 from exavatar_release_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD = ctypes.c_void_p(0x1000)      # never dereferenced: every call below fails validation first
-
-
-def _declared():
-    src = open(os.path.join(ROOT, 'include', 'exa_knn.h')).read()
-    return sorted(set(re.findall(r'\b(exa_knn_\w+)\s*\(', re.sub(r'/\*.*?\*/', '', src, flags=re.S))))
-
-
-def test_every_declared_function_is_exported_and_bound():
-    lib = _lib.load()
-    names = _declared()
-    assert set(names) == set(_lib.KNN_SIGNATURES)
-    assert len(names) == 5
-    for n in names:
-        assert hasattr(lib, n), n
-    assert lib.exa_knn_version() == 100
-    # the knn ABI stays out of exa_raster.h's table
-    assert not any(n.startswith('exa_knn') for n in _lib.SIGNATURES)
 
 
 def _size(N, P1, P2, K):

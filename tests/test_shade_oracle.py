@@ -1,11 +1,8 @@
 """CPU checks of the Phong-shaded render: the float64 oracle tests/shade_oracle.py against answers worked out by hand,
-the package's composite against the reference's four lines, and the C ABI of the shaded entry points (symbols, struct
-layout, argument checks that return before any launch)."""
+the package's composite against the reference's four lines, and the argument checks of the shaded entry points that
+return before any launch (their symbols and struct layout: tests/test_abi.py)."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +12,6 @@ from exavatar_release_amd import _lib, mesh
 from tests import mesh_oracle as mo
 from tests import shade_oracle as so
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, W = 12, 16
 FOCAL, PRINCPT = 10.0, (8.0, 6.0)
 
@@ -147,26 +143,6 @@ def test_composite_is_the_reference_composite(dtype, blend_ratio):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------
-def test_shaded_symbols_are_bound_and_resolve():
-    for name in ('exa_mesh_vertex_normals', 'exa_mesh_forward_shaded'):
-        assert name in _lib.MESH_SIGNATURES
-        assert getattr(_lib.load(), name) is not None
-
-
-def test_shading_struct_layout_matches_the_header(tmp_path):
-    if shutil.which('gcc') is None:
-        pytest.skip('no gcc')
-    fields = [f[0] for f in _lib.ExaMeshShading._fields_]
-    src = tmp_path / 'layout.c'
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "exa_mesh.h"\nint main(void) {\n'
-                   '  printf("%%d", (int)sizeof(ExaMeshShading));\n%s  return 0;\n}\n'
-                   % ''.join('  printf(" %%d", (int)offsetof(ExaMeshShading, %s));\n' % f for f in fields))
-    exe = tmp_path / 'layout'
-    subprocess.run(['gcc', '-std=c99', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out == [ctypes.sizeof(_lib.ExaMeshShading)] + [getattr(_lib.ExaMeshShading, f).offset for f in fields]
-
-
 def _shading(shininess=0.0):
     sh = _lib.ExaMeshShading()
     sh.light_location[:] = [0.0, -1.0, 0.0]

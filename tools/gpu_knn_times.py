@@ -61,7 +61,7 @@ def visited_fraction(p1, p2, K):
     idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
     waves = (P1 + 63) // 64
     refs = torch.zeros((N, waves), dtype=torch.int32, device=dev)
-    _lib.check_knn(_lib.load().exa_knn_forward(N, P1, P2, K, _ptr(p1), _ptr(p2), 0, _ptr(ws), nbytes, _ptr(dists),
+    _lib.KNN.check(_lib.load().exa_knn_forward(N, P1, P2, K, _ptr(p1), _ptr(p2), 0, _ptr(ws), nbytes, _ptr(dists),
                                                _ptr(idx), _ptr(refs), _stream_ptr(dev)))
     qcount = torch.full((waves,), 64.0, dtype=torch.float64, device=dev)
     qcount[-1] = P1 - 64 * (waves - 1)

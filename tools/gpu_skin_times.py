@@ -99,7 +99,7 @@ def main():
     det = [p.detach() for p in points]
 
     def hip_bwd():
-        _lib.check_skin(_lib.load().exa_skin_backward(V, 2, J, V, _ptrs(det), _ptr(W), _ptr(idx), _ptr(T.detach()),
+        _lib.SKIN.check(_lib.load().exa_skin_backward(V, 2, J, V, _ptrs(det), _ptr(W), _ptr(idx), _ptr(T.detach()),
                                                       _ptr(Rinv), _ptrs(grads), _ptrs(gp), _ptr(gT), _ptr(gtr), _ptr(ws),
                                                       nbytes, _stream_ptr(dev)))
 

@@ -91,7 +91,7 @@ def main():
     gf = torch.empty_like(face)
 
     def hip_bwd():
-        _lib.check_triplane(_lib.load().exa_triplane_backward(
+        _lib.TRIPLANE.check(_lib.load().exa_triplane_backward(
             tf.num_rows, 32, 128, 128, _ptr(tf.coords), _ptr(gout), _ptr(p.entries), _ptr(p.seg_entry), _ptr(p.tex_seg),
             _ptr(p.wg_tex), p.num_wg, p.max_wg_segments, _ptr(gb), _ptr(gf), _stream_ptr(dev)))
 
