@@ -31,6 +31,11 @@ and for the four MLPs between them (``make_linear_layers(..., use_gn=True)`` + h
 ``avatar/common/nets/module.py:279-287,459-509,524-528``):
 
     from exavatar_release_amd import FusedMLP
+
+and for the mesh Laplacian regulariser behind their outputs (``LaplacianReg``, reference
+``avatar/common/nets/loss.py:97-131``, called at ``avatar/main/model.py:237-247``):
+
+    from exavatar_release_amd import LaplacianReg
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -44,10 +49,11 @@ from .knn import knn_points
 from .triplane import TriplaneFeatures
 from .skinning import skin_points
 from .mlp import FusedMLP
+from .mesh_reg import LaplacianReg, mesh_laplacian_loss
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
-           'skin_points', 'FusedMLP']
+           'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss']

@@ -218,7 +218,7 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
             ExaRasterBackwardJob))
 
-# the triangle rasterizer of the face render
+# the triangle rasterizer of the face render, and the mesh Laplacian regulariser
 MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -230,6 +230,11 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_vertex_normals': (ctypes.c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_mesh_forward_shaded': (ctypes.c_int, [_GP, _SHP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
+    # the mesh Laplacian regulariser (csrc/mesh_reg.hip)
+    'exa_mesh_neighbor_transpose': (ctypes.c_int, [_I32, _I32, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_laplacian_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 8),
+    'exa_mesh_laplacian_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_mesh_laplacian_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 7 + [_U64, c_void_p, c_void_p]),
 }, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
 
 # the K-nearest-neighbour search
@@ -309,6 +314,12 @@ def skin_workspace_size(V, J):
 def knn_workspace_size(N, P1, P2, K):
     out = _U64()
     KNN.check(load().exa_knn_workspace_size(N, P1, P2, K, ctypes.byref(out)))
+    return int(out.value)
+
+
+def laplacian_workspace_size(B, V, C):
+    out = _U64()
+    MESH.check(load().exa_mesh_laplacian_workspace_size(B, V, C, ctypes.byref(out)))
     return int(out.value)
 
 

@@ -45,6 +45,8 @@ SOURCES = {
     'skinning.hip': ['-ffp-contract=off'],
     # the fused MLP's VALU arithmetic (GroupNorm, its backward) is defined operation by operation (include/exa_mlp.h)
     'mlp.hip': ['-ffp-contract=off'],
+    # the mesh Laplacian and its backward are defined operation by operation (include/exa_mesh.h)
+    'mesh_reg.hip': ['-ffp-contract=off'],
 }
 
 

@@ -6,6 +6,8 @@
 //   fail(code, what)      "exa_knn: <what>", returns code
 //   fail_hip(e, where)    "exa_knn: HIP error <e> (<text>) in <where>", returns (int)e
 //   launched(kernel)      0, or fail_hip() of hipGetLastError() for the kernel just enqueued
+// An ABI spread over two sources (exa_mesh: mesh_raster.hip and mesh_reg.hip) defines the buffer in one of them and says
+// EXA_ABI_STATUS_SHARED("exa_mesh") in the other, inside the same namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +37,14 @@ inline unsigned ceil_div(int64_t n, int64_t block) { return (unsigned)((n + bloc
 
 #define EXA_ABI_STATUS(ABI)                                                                                            \
     thread_local char g_err[exa::ABI_ERR_BYTES] = "";                                                                  \
+    EXA_ABI_STATUS_FUNCTIONS(ABI)
+
+// A second source of the same ABI (same namespace): the buffer is the first source's, the three functions are the same.
+#define EXA_ABI_STATUS_SHARED(ABI)                                                                                     \
+    extern thread_local char g_err[exa::ABI_ERR_BYTES];                                                                \
+    EXA_ABI_STATUS_FUNCTIONS(ABI)
+
+#define EXA_ABI_STATUS_FUNCTIONS(ABI)                                                                                  \
     inline int fail(int code, const char* what) { return exa::abi_fail(g_err, ABI, code, what); }                      \
     inline int fail_hip(hipError_t e, const char* where) { return exa::abi_fail_hip(g_err, ABI, e, where); }           \
     inline int launched(const char* kernel) {                                                                          \

@@ -1,0 +1,207 @@
+"""HIP mesh Laplacian regulariser: a drop-in for ExAvatar's ``LaplacianReg`` with a bit-reproducible backward.
+
+* ``LaplacianReg(vertex_num, face, neighbor_max_num=10)`` -- reference ``avatar/common/nets/loss.py:97-131``, called six
+  times per iteration at ``avatar/main/model.py:237-247``.  ``forward(out, target)`` (``target`` may be ``None``) returns
+  the elementwise ``[B, V, C]`` loss; an optional third argument ``weight`` multiplies a per-vertex weight into it inside
+  the kernel.  ``neighbor_idxs`` (int64) and ``neighbor_weights`` are attributes, as in the reference.
+* ``mesh_laplacian_loss(out, target, neighbor_idxs, neighbor_weights, weight=None)`` -- the same for a caller's own table.
+
+The kernels are ``csrc/mesh_reg.hip`` behind ``include/exa_mesh.h``; ROCm float32 tensors only, no CPU path.  The CPU
+restatement that pins them is ``tests/lap_oracle.py``.
+
+Semantics
+---------
+``lap(x)[b,v,c] = x[b,v,c]``, then for the K slots of vertex v's table row in order ``lap += x[b, idx[v,k], c] * w[v,k]``;
+``d = lap(out)`` or ``lap(out) - lap(target)`` (``target`` ``[B, V, C]`` or ``[1, V, C]``); ``loss = d * d`` and, with a
+weight, ``loss * weight[v]``.  Every operation is rounded in fp32 without fused multiply-adds, in this order.  PyTorch
+evaluates the reference's ``(x[:, idx] * w).sum(2)`` in an order of its own, so the two differ by rounding; the bound is
+derived in ``tests/lap_oracle.py``.  Padded slots (the vertex itself, weight 0) are evaluated like any other, as the
+reference does.
+
+The table is the reference's, element for element.  ``get_neighbor`` keeps ``list(adj[v])[:neighbor_max_num]`` of a
+Python ``set``, so the slot order -- and, for a vertex with more neighbours than slots, WHICH neighbours are kept -- is
+CPython's set iteration order, which is not ascending.  The constructor therefore fills one Python set per vertex with
+the same operations in the same order (about 2 s for 90 000 vertices, once per model).
+
+The backward gathers, for every vertex, the slots that name it from a transposed table in CSR form (ascending row, then
+slot; built once per table and device by ``exa_mesh_neighbor_transpose``) -- no atomics and a summation order the header
+states, so the same inputs give the same bits on every call by construction, where the order of the reference's
+``index_put_(accumulate=True)`` is PyTorch's own business.  ``target`` and ``weight`` are data in the reference and get no
+gradient.
+
+Each call allocates its outputs (backward: a workspace from the torch allocator) and launches one kernel forward, two
+backward, on the current stream; nothing synchronises once the tables are cached, so calls can be captured into a hipGraph.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._device import _ptr, _stream_ptr, _workspace, need_rocm
+
+MAX_CHANNELS = 8          # EXA_MESH_LAP_MAX_CHANNELS
+MAX_NEIGHBORS = 16        # EXA_MESH_LAP_MAX_NEIGHBORS
+
+
+def neighbor_table(vertex_num, face, neighbor_max_num=10):
+    """The reference's ``get_neighbor``: ``(neighbor_idxs [V, K] int64, neighbor_weights [V, K] float32)`` as numpy
+    arrays.  Row v holds ``list(adj[v])[:K]`` -- adj[v] a Python set filled in ascending face order -- with weight
+    ``-1 / n`` in those n slots, and v itself with weight 0 in the rest."""
+    V, K = int(vertex_num), int(neighbor_max_num)
+    if V < 0 or not 1 <= K <= MAX_NEIGHBORS:
+        raise ValueError('LaplacianReg: vertex_num must be >= 0 and neighbor_max_num 1 .. %d' % MAX_NEIGHBORS)
+    faces = (face.detach().cpu().numpy() if isinstance(face, torch.Tensor) else np.asarray(face)).tolist()
+    adj = [set() for _ in range(V)]
+    for f in faces:
+        corners = set(f)
+        for v in f:
+            if not 0 <= v < V:
+                raise ValueError('LaplacianReg: face index %d is outside [0, %d)' % (v, V))
+            # the set operations the reference performs, so that the iteration order below is the reference's
+            adj[v] |= corners - {v}
+    idxs = np.tile(np.arange(V, dtype=np.int64)[:, None], (1, K))
+    weights = np.zeros((V, K), dtype=np.float32)
+    for v in range(V):
+        n = min(len(adj[v]), K)
+        if n == 0:
+            raise ValueError('LaplacianReg: vertex %d belongs to no face (the reference divides by zero there)' % v)
+        idxs[v, :n] = list(adj[v])[:n]
+        weights[v, :n] = -1.0 / n
+    return idxs, weights
+
+
+def _device_tables(idxs, weights, device):
+    """(idx [V, K] int32, w [V, K] float32, CSR offsets [V + 1], CSR entries [V * K]) on ``device``."""
+    idx32 = np.ascontiguousarray(idxs.detach().cpu().numpy(), dtype=np.int64)
+    if idx32.size and (idx32.min() < 0 or idx32.max() >= idx32.shape[0]):
+        bad = idx32[(idx32 < 0) | (idx32 >= idx32.shape[0])][0]
+        raise ValueError('mesh_laplacian_loss: neighbour index %d is outside [0, %d)' % (bad, idx32.shape[0]))
+    idx32 = idx32.astype(np.int32)
+    V, K = idx32.shape
+    offsets = np.zeros(V + 1, dtype=np.int32)
+    entries = np.zeros(max(V * K, 1), dtype=np.int32)
+    _lib.MESH.check(_lib.load().exa_mesh_neighbor_transpose(V, K, idx32.ctypes.data, offsets.ctypes.data,
+                                                            entries.ctypes.data))
+    return (torch.from_numpy(idx32).to(device), weights.detach().to(device=device, dtype=torch.float32).contiguous(),
+            torch.from_numpy(offsets).to(device), torch.from_numpy(entries).to(device))
+
+
+class _Laplacian(torch.autograd.Function):
+    """out [B, V, C], target [Bt, V, C] or None, weight [V] or None (float32, contiguous), the four device tables
+    -> (loss [B, V, C], d [B, V, C]); d is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, out, target, weight, idx, w, offsets, entries):
+        B, V, C = out.shape
+        K = idx.shape[1]
+        dev = out.device
+        loss, d = torch.empty_like(out), torch.empty_like(out)
+        with torch.cuda.device(dev):
+            _lib.MESH.check(_lib.load().exa_mesh_laplacian_forward(
+                B, target.shape[0] if target is not None else 1, V, C, K, _ptr(out), _ptr(target), _ptr(idx), _ptr(w),
+                _ptr(weight), _ptr(loss), _ptr(d), _stream_ptr(dev)))
+        ctx.has_weight = weight is not None
+        ctx.save_for_backward(d, w, offsets, entries, weight if weight is not None else w.new_empty(0))
+        ctx.mark_non_differentiable(d)
+        return loss, d
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_d):
+        if grad_loss is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        d, w, offsets, entries, weight = ctx.saved_tensors
+        weight = weight if ctx.has_weight else None
+        B, V, C = d.shape
+        dev = d.device
+        grad_loss = grad_loss.to(torch.float32).contiguous()
+        gout = torch.empty_like(d)
+        nbytes = _lib.laplacian_workspace_size(B, V, C)
+        ws = _workspace(nbytes, dev)
+        with torch.cuda.device(dev):
+            _lib.MESH.check(_lib.load().exa_mesh_laplacian_backward(
+                B, V, C, w.shape[1], _ptr(d), _ptr(grad_loss), _ptr(w), _ptr(weight), _ptr(offsets), _ptr(entries),
+                _ptr(ws) if nbytes else None, nbytes, _ptr(gout), _stream_ptr(dev)))
+        return (gout,) + (None,) * 6
+
+
+def _check_inputs(out, target, weight, V, what):
+    for name, x in (('out', out), ('target', target), ('weight', weight)):
+        if x is None and name != 'out':
+            continue
+        if not isinstance(x, torch.Tensor):
+            raise TypeError('%s: %s must be a tensor' % (what, name))
+        need_rocm(x.device, what)
+        if x.dtype != torch.float32:
+            raise ValueError('%s: %s must be float32 (it is %s)' % (what, name, x.dtype))
+        if x.device != out.device:
+            raise ValueError('%s: %s is not on the device of out' % (what, name))
+    # what the reference holds as data gets no gradient
+    for name, x in (('target', target), ('weight', weight)):
+        if x is not None and x.requires_grad:
+            raise ValueError('%s: %s is data in the reference and gets no gradient; detach it' % (what, name))
+    if out.dim() != 3 or out.shape[1] != V or not 1 <= out.shape[2] <= MAX_CHANNELS:
+        raise ValueError('%s: out must be [B, V, C] with V = %d and 1 <= C <= %d (it is %s)'
+                         % (what, V, MAX_CHANNELS, tuple(out.shape)))
+    if target is not None and (target.dim() != 3 or tuple(target.shape[1:]) != tuple(out.shape[1:])
+                               or target.shape[0] not in (1, out.shape[0])):
+        raise ValueError('%s: target must be [B, V, C] or [1, V, C] like out (it is %s)' % (what, tuple(target.shape)))
+    if weight is not None:
+        if tuple(weight.shape) not in ((V,), (1, V, 1), (V, 1)):
+            raise ValueError('%s: weight must be [V], [1, V, 1] or [V, 1] with V = %d (it is %s)'
+                             % (what, V, tuple(weight.shape)))
+        weight = weight.reshape(V).contiguous()
+    return out.contiguous(), None if target is None else target.contiguous(), weight
+
+
+_tables = {}     # functional form: (id(idxs), id(weights), their versions and storage, device) -> (idxs, weights, tables)
+
+
+def mesh_laplacian_loss(out, target, neighbor_idxs, neighbor_weights, weight=None, return_d=False):
+    """``LaplacianReg.forward`` for a caller's own table: ``neighbor_idxs`` [V, K] (an integer tensor, every entry in
+    [0, V)) and ``neighbor_weights`` [V, K] float32, K <= 16, with general weights.  The device copies and the transposed
+    table are cached per pair of tensor objects and device (an in-place change of either rebuilds them).  Returns the
+    ``[B, V, C]`` loss, or ``(loss, d)`` with ``return_d`` (``d`` is what is squared; it carries no gradient)."""
+    what = 'mesh_laplacian_loss'
+    if not isinstance(neighbor_idxs, torch.Tensor) or not isinstance(neighbor_weights, torch.Tensor) \
+            or neighbor_idxs.dim() != 2 or neighbor_idxs.shape != neighbor_weights.shape \
+            or neighbor_idxs.dtype not in (torch.int32, torch.int64) or not 1 <= neighbor_idxs.shape[1] <= MAX_NEIGHBORS:
+        raise ValueError('%s: neighbor_idxs (int32 / int64) and neighbor_weights must be [V, K] tensors, 1 <= K <= %d'
+                         % (what, MAX_NEIGHBORS))
+    if neighbor_weights.requires_grad:
+        raise ValueError('%s: neighbor_weights is data in the reference and gets no gradient; detach it' % what)
+    out, target, weight = _check_inputs(out, target, weight, neighbor_idxs.shape[0], what)
+    key = (id(neighbor_idxs), id(neighbor_weights), neighbor_idxs._version, neighbor_weights._version,
+           neighbor_idxs.data_ptr(), neighbor_weights.data_ptr(), str(out.device))
+    hit = _tables.get(key)
+    if hit is None:
+        if len(_tables) > 16:
+            _tables.clear()
+        # the entry holds the two tensors, so that their ids stay theirs while it lives
+        hit = _tables[key] = (neighbor_idxs, neighbor_weights, _device_tables(neighbor_idxs, neighbor_weights, out.device))
+    loss, d = _Laplacian.apply(out, target, weight, *hit[2])
+    return (loss, d) if return_d else loss
+
+
+class LaplacianReg(nn.Module):
+    """Drop-in for the reference's ``LaplacianReg`` (``loss.py:97-131``): same constructor, same ``forward(out, target)``
+    and result, same ``neighbor_idxs`` / ``neighbor_weights`` attributes (on the current ROCm device when there is one,
+    as the reference's ``.cuda()`` puts them).  ``forward`` takes an optional per-vertex ``weight``."""
+
+    def __init__(self, vertex_num, face, neighbor_max_num=10):
+        super(LaplacianReg, self).__init__()
+        self.neighbor_idxs, self.neighbor_weights = self.get_neighbor(vertex_num, face, neighbor_max_num)
+        self._tables = {}     # device -> (idx int32, w, CSR offsets, CSR entries), built on first use
+
+    def get_neighbor(self, vertex_num, face, neighbor_max_num=10):
+        idxs, weights = neighbor_table(vertex_num, face, neighbor_max_num)
+        idxs, weights = torch.from_numpy(idxs), torch.from_numpy(weights)
+        if torch.cuda.is_available():
+            idxs, weights = idxs.cuda(), weights.cuda()
+        return idxs, weights
+
+    def forward(self, out, target, weight=None):
+        out, target, weight = _check_inputs(out, target, weight, self.neighbor_idxs.shape[0], 'LaplacianReg')
+        tables = self._tables.get(out.device)
+        if tables is None:
+            tables = self._tables[out.device] = _device_tables(self.neighbor_idxs, self.neighbor_weights, out.device)
+        return _Laplacian.apply(out, target, weight, *tables)[0]

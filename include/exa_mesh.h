@@ -11,6 +11,12 @@
  * the reference's `render_mesh` (avatar/common/utils/vis.py:73-109: pytorch3d `SoftPhongShader`, `PointLights`,
  * `Materials`, `TexturesVertex` of ones), under `exavatar_release_amd.mesh.shade_mesh` / `render_mesh`.
  *
+ * The mesh regulariser lives here too: `exa_mesh_neighbor_transpose` + `exa_mesh_laplacian_*` are the reference's
+ * `LaplacianReg` (avatar/common/nets/loss.py:97-131) under `exavatar_release_amd.mesh_reg.LaplacianReg`.  It is a
+ * per-vertex gather over a fixed-order CSR like `exa_mesh_vertex_normals`, and the ABI test pins one ABI per header
+ * and the set of headers, so it joins this ABI instead of opening a seventh.  The additions change no existing
+ * prototype or struct: EXA_MESH_VERSION stays 100.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -132,6 +138,50 @@ int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offset
  *   image            [dev] [N, H, W, 3] (channel-last): the shaded colour, `background` at empty pixels (required). */
 int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shading, const float* normals, void* face_ws,
                             void* bin_ws, int64_t* pix_to_face, float* zbuf, float* image, void* stream);
+
+/* ---- Mesh Laplacian regulariser (reference LaplacianReg) ------------------------------------------------------------
+ * x [B, V, C] fp32 (1 <= C <= EXA_MESH_LAP_MAX_CHANNELS), a neighbour table nbr_idx [V, K] int32 / nbr_w [V, K] fp32
+ * (1 <= K <= EXA_MESH_LAP_MAX_NEIGHBORS; general weights, the reference's are -1/n in the first n slots and its
+ * padded slots hold the vertex itself with weight 0).  V * K <= 2^28.
+ *
+ * Arithmetic, every operation rounded in fp32, no fused multiply-add, in exactly this order:
+ *   lap(x)[b,v,c] = x[b,v,c];  for k = 0 .. K-1 in order:  lap = lap + x[b, nbr_idx[v,k], c] * nbr_w[v,k]
+ *   d    = lap(out)                  without a target
+ *   d    = lap(out) - lap(target)    with a target [Bt, V, C], Bt == B or Bt == 1 (broadcast over b)
+ *   loss = d * d,  then  loss = loss * weight[v]  with a weight [V]
+ * Padded slots are evaluated like any other slot.  A slot whose index lies outside [0, V) reads nothing and
+ * contributes NaN.
+ *
+ * Backward, atomic-free and bit-deterministic.  g[b,u,c] = (grad_loss[b,u,c] * weight[u]) * (2 * d[b,u,c]) (the first
+ * product only with a weight), then
+ *   dL_dout[b,v,c] = g[b,v,c];  for every (u, k) with nbr_idx[u,k] == v, ascending u then ascending k:
+ *                    dL_dout = dL_dout + nbr_w[u,k] * g[b,u,c]
+ * over the transposed table of exa_mesh_neighbor_transpose.  target and weight get no gradient.  B == 0 or V == 0 is
+ * a successful no-op in every call. */
+#define EXA_MESH_LAP_MAX_CHANNELS 8
+#define EXA_MESH_LAP_MAX_NEIGHBORS 16
+
+/* Host-side helper: the incoming lists of the backward, in CSR form: for every vertex v the slots (u, k) with
+ * nbr_idx[u,k] == v, ascending u then k.  `nbr_idx` [V,K], `offsets` [V+1] and `entries` [V*K] (value u * K + k) are
+ * HOST memory.  EXA_MESH_E_INVALID, with a message naming it, for the first index outside [0, V).  Build once per
+ * topology and copy to the device. */
+int exa_mesh_neighbor_transpose(int32_t V, int32_t K, const int32_t* nbr_idx, int32_t* offsets, int32_t* entries);
+
+/* One launch.  out [dev] [B,V,C]; target [dev] [Bt,V,C] or NULL (then Bt is ignored); nbr_idx, nbr_w [dev] [V,K];
+ * weight [dev] [V] or NULL; loss, d [dev] [B,V,C], fully written (d is what the backward reads). */
+int exa_mesh_laplacian_forward(int32_t B, int32_t Bt, int32_t V, int32_t C, int32_t K, const float* out,
+                               const float* target, const int32_t* nbr_idx, const float* nbr_w, const float* weight,
+                               float* loss, float* d, void* stream);
+
+/* Bytes of the backward's workspace (g, staged by its first launch). */
+int exa_mesh_laplacian_workspace_size(int32_t B, int32_t V, int32_t C, uint64_t* out_bytes);
+
+/* Two launches.  d [dev] the forward's; grad_loss [dev] [B,V,C]; nbr_w, weight as in the forward; in_offsets [dev]
+ * [V+1] and in_entries [dev] [V*K]: exa_mesh_neighbor_transpose's CSR; ws [dev] of ws_bytes >=
+ * exa_mesh_laplacian_workspace_size (NULL only when that is 0); dL_dout [dev] [B,V,C], fully written. */
+int exa_mesh_laplacian_backward(int32_t B, int32_t V, int32_t C, int32_t K, const float* d, const float* grad_loss,
+                                const float* nbr_w, const float* weight, const int32_t* in_offsets,
+                                const int32_t* in_entries, void* ws, uint64_t ws_bytes, float* dL_dout, void* stream);
 
 #ifdef __cplusplus
 }
