@@ -36,6 +36,11 @@ and for the mesh Laplacian regulariser behind their outputs (``LaplacianReg``, r
 ``avatar/common/nets/loss.py:97-131``, called at ``avatar/main/model.py:237-247``):
 
     from exavatar_release_amd import LaplacianReg
+
+and for the blend-shape offsets on the upsampled mesh (the pose correctives of ``get_mean_offset_offset`` and the
+expression offsets, reference ``avatar/common/nets/module.py:473-493,537``):
+
+    from exavatar_release_amd import BlendShapes
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -50,10 +55,12 @@ from .triplane import TriplaneFeatures
 from .skinning import skin_points
 from .mlp import FusedMLP
 from .mesh_reg import LaplacianReg, mesh_laplacian_loss
+from .blend_shapes import BlendShapes, BlendTable, blend_offsets
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
            'render_iteration', 'ITERATION_RENDERS', 'GraphedRenderer', 'GraphedIteration', 'StaticRender', 'required_capacity',
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
-           'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss']
+           'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
+           'blend_offsets']

@@ -218,7 +218,7 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
             ExaRasterBackwardJob))
 
-# the triangle rasterizer of the face render, and the mesh Laplacian regulariser
+# the triangle rasterizer of the face render, the mesh Laplacian regulariser and the blend-shape offsets
 MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -235,7 +235,11 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_laplacian_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 8),
     'exa_mesh_laplacian_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(_U64)]),
     'exa_mesh_laplacian_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 7 + [_U64, c_void_p, c_void_p]),
-}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
+    # the blend-shape offsets (csrc/blend_shapes.hip)
+    'exa_mesh_blend_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 8),
+    'exa_mesh_blend_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_mesh_blend_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 6 + [_U64, c_void_p, c_void_p, c_void_p]),
+},_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
 
 # the K-nearest-neighbour search
 KNN = Abi('exa_knn', 'exa_knn.h', 100, {
@@ -320,6 +324,12 @@ def knn_workspace_size(N, P1, P2, K):
 def laplacian_workspace_size(B, V, C):
     out = _U64()
     MESH.check(load().exa_mesh_laplacian_workspace_size(B, V, C, ctypes.byref(out)))
+    return int(out.value)
+
+
+def blend_workspace_size(K, N):
+    out = _U64()
+    MESH.check(load().exa_mesh_blend_workspace_size(K, N, ctypes.byref(out)))
     return int(out.value)
 
 

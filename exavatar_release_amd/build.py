@@ -47,6 +47,8 @@ SOURCES = {
     'mlp.hip': ['-ffp-contract=off'],
     # the mesh Laplacian and its backward are defined operation by operation (include/exa_mesh.h)
     'mesh_reg.hip': ['-ffp-contract=off'],
+    # the blend-shape offsets and their backward are defined operation by operation (include/exa_mesh.h)
+    'blend_shapes.hip': ['-ffp-contract=off'],
 }
 
 

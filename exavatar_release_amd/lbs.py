@@ -13,7 +13,8 @@ skinned to at most four joints, one rigid transform per joint composed along the
 
 What the reference also does here and this module does not: triplane feature lookup + the offset / scale / colour MLPs
 (their outputs are plain leaf parameters here), the nearest-vertex search (``knn_points``; stand-in in
-``p3d_standins.py``), expression blend shapes.
+``p3d_standins.py``), the pose correctives and the expression blend shapes (``module.py:484-493,537``; their HIP drop-in
+is ``exavatar_release_amd.BlendShapes``, ``blend_shapes.py``).
 """
 import math
 

@@ -17,6 +17,9 @@
  * and the set of headers, so it joins this ABI instead of opening a seventh.  The additions change no existing
  * prototype or struct: EXA_MESH_VERSION stays 100.
  *
+ * So do the blend-shape offsets of the same upsampled mesh: `exa_mesh_blend_*` are the reference's pose correctives and
+ * expression offsets (avatar/common/nets/module.py:484-493,537) under `exavatar_release_amd.blend_shapes.BlendShapes`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -182,6 +185,58 @@ int exa_mesh_laplacian_workspace_size(int32_t B, int32_t V, int32_t C, uint64_t*
 int exa_mesh_laplacian_backward(int32_t B, int32_t V, int32_t C, int32_t K, const float* d, const float* grad_loss,
                                 const float* nbr_w, const float* weight, const int32_t* in_offsets,
                                 const int32_t* in_entries, void* ws, uint64_t ws_bytes, float* dL_dout, void* stream);
+
+/* ---- Blend-shape offsets (reference pose correctives and expression offsets) ---------------------------------------
+ * The reference's `torch.matmul(pose, pose_dirs)` with its hand / face mask (module.py:484-493) and its
+ * `(expr[None,None,:] * expr_dirs).sum(2)` (module.py:537) are one operation: a coefficient vector coef [K]
+ * (1 <= K <= EXA_MESH_BLEND_MAX_K) times a matrix of which only some columns matter, scattered to a flat output [M]
+ * (M = 3 V for a [V, 3] result, M <= 2^30).  The matrix travels compacted, as a plan built once per model
+ * (exavatar_release_amd.blend_shapes builds it):
+ *   table [K, ld]  feature-major, fp32: column s < N is kept column cols[s] of the full matrix; ld >= N is a multiple
+ *                  of 4 (rows start on 16-byte boundaries; the pointer is 16-byte aligned); columns N .. ld-1 are zero.
+ *   cols  [N]      int32, ascending: compact column -> flat output index in [0, M).
+ *   inv   [M]      int32: flat output index -> compact column, -1 where no column covers it.
+ * Like exa_mesh_laplacian_* this is a per-vertex operation on the upsampled mesh, and the ABI test pins one ABI per
+ * header and the set of headers, so it joins this ABI; no existing prototype changes: EXA_MESH_VERSION stays 100.
+ *
+ * Forward.  Every operation rounded in fp32, no fused multiply-add, in exactly this order, which depends on K alone:
+ * the rows are cut into EXA_MESH_BLEND_SEGMENTS = 8 segments of L = ceil(K / 8) rows, segment s = rows s L ..
+ * min(K, (s + 1) L) - 1 (empty where s L >= K);
+ *   p_s = +0.0;  for k in segment s, ascending:  p_s = p_s + coef[k] * table[k, col]
+ *   sum = p_0;   for s = 1 .. 7 in order:        sum = sum + p_s
+ *   out[cols[col]] = sum, out_masked[cols[col]] = +0.0                 for every column col < N
+ *   out[j] = out_masked[j] = base[j]  (+0.0 without a base)            for every j with inv[j] < 0
+ * Every element of out and out_masked is written exactly once; nothing is memset.  This is the reference's
+ * (output, mean_offset_offset) pair of module.py:493 with base = mean_offset_offset, up to the sign of a zero.
+ *
+ * Backward, atomic-free and bit-deterministic.  With g = g_out gathered through cols (0 for columns >= N):
+ *   dL_dbase[j] = g_out[j] + g_masked[j] where inv[j] < 0 (one of them alone where the other is NULL), +0.0 elsewhere.
+ *   dL_dcoef[k]: the compact columns are cut into chunks of EXA_MESH_BLEND_CHUNK = 1024.  In a chunk, lane t of 256
+ *     owns columns 4 t .. 4 t + 3 and forms q_t = ((T0 g0 + T1 g1) + T2 g2) + T3 g3; the 64 lanes of each of the four
+ *     waves (lanes 64 w .. 64 w + 63) are added as a tree, for off = 32, 16, 8, 4, 2, 1 in order q_i = q_i + q_(i+off)
+ *     for i < off; the chunk's partial is ((w_0 + w_1) + w_2) + w_3; and
+ *     dL_dcoef[k] = +0.0, then for chunk = 0, 1, .. in order: dL_dcoef[k] = dL_dcoef[k] + partial[chunk, k].
+ * The table is data: it gets no gradient.  M == 0 is a successful no-op; N == 0 is valid (everything is uncovered). */
+#define EXA_MESH_BLEND_MAX_K 512
+#define EXA_MESH_BLEND_SEGMENTS 8
+#define EXA_MESH_BLEND_CHUNK 1024
+
+/* One launch.  coef [dev] [K]; table [dev] [K, ld]; cols [dev] [N]; inv [dev] [M]; base [dev] [M] or NULL;
+ * out [dev] [M]; out_masked [dev] [M] or NULL (not wanted).  table and cols may be NULL when N == 0. */
+int exa_mesh_blend_forward(int32_t K, int32_t N, int32_t ld, int32_t M, const float* coef, const float* table,
+                           const int32_t* cols, const int32_t* inv, const float* base, float* out, float* out_masked,
+                           void* stream);
+
+/* Bytes of the backward's workspace (the chunks' partials, [ceil(N / 1024), K]).  Host only. */
+int exa_mesh_blend_workspace_size(int32_t K, int32_t N, uint64_t* out_bytes);
+
+/* At most two launches.  table, cols, inv as in the forward; g_out, g_masked [dev] [M]: the gradients of out and
+ * out_masked (g_masked may be NULL; g_out may be NULL when dL_dcoef is); ws [dev] of ws_bytes >=
+ * exa_mesh_blend_workspace_size, needed for dL_dcoef only (NULL when that size is 0); dL_dcoef [dev] [K] or NULL (not
+ * wanted: the table is not read); dL_dbase [dev] [M] or NULL (not wanted).  Both are fully written. */
+int exa_mesh_blend_backward(int32_t K, int32_t N, int32_t ld, int32_t M, const float* table, const int32_t* cols,
+                            const int32_t* inv, const float* g_out, const float* g_masked, void* ws, uint64_t ws_bytes,
+                            float* dL_dcoef, float* dL_dbase, void* stream);
 
 #ifdef __cplusplus
 }
