@@ -1,8 +1,11 @@
 """What every feature module needs to hand torch tensors to the C ABIs: data pointers, the current stream, workspaces
-from the torch allocator, the ROCm-only guard, and the package's run-time ``config``."""
+from the torch allocator, the launch of a stream-taking call, incoming gradients, the argument checks the features share
+and the package's run-time ``config``."""
 import ctypes
 
 import torch
+
+from . import _lib
 
 
 class _Config:
@@ -60,6 +63,55 @@ def _workspace(nbytes, device):
     return ws
 
 
+class _NoCtx:
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NO_CTX = _NoCtx()
+
+
+def _on_device(device):
+    """``torch.cuda.device(device)`` only when it is not the current device already (the context manager costs ~10 us
+    per entry, twice per render, in an eager training loop)."""
+    return _NO_CTX if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+
+
+def launch(abi, name, device, *args):
+    """One stream-taking call of a C ABI: ``device`` is made current, ``name(*args, stream)`` is enqueued on its current
+    stream and the status goes to ``abi.check``."""
+    with _on_device(device):
+        abi.check(getattr(_lib.load(), name)(*args, _stream_ptr(device)))
+
+
+def grad_in(g):
+    """An incoming gradient as a contiguous float32 tensor (``g`` itself when it is one already); None stays None."""
+    return None if g is None else g.to(torch.float32).contiguous()
+
+
 def need_rocm(device, what):
     if device.type != 'cuda':
         raise RuntimeError('exavatar_release_amd: %s runs on a ROCm device only (no CPU path)' % what)
+
+
+def check_tensor(what, name, x, f32=True, rocm=False, on=None):
+    """The argument checks the features share, in this order: ``x`` is a tensor; with ``rocm``, it is on a ROCm device;
+    with ``f32``, it is float32; with ``on`` = (anchor tensor, its name), it is on the anchor's device."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('%s: %s must be a tensor' % (what, name))
+    if rocm:
+        need_rocm(x.device, what)
+    if f32 and x.dtype != torch.float32:
+        raise ValueError('%s: %s must be float32 (it is %s)' % (what, name, x.dtype))
+    if on is not None and x.device != on[0].device:
+        raise ValueError('%s: %s is not on the device of %s' % (what, name, on[1]))
+
+
+def check_no_grad(what, name, x, kind='data'):
+    """What the reference holds as ``kind`` (data, a buffer, camera data) gets no gradient: a tensor that requires one is
+    refused.  Anything else passes (None included)."""
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        raise ValueError('%s: %s is %s in the reference and gets no gradient; detach it' % (what, name, kind))

@@ -309,40 +309,42 @@ def load():
     return lib
 
 
-def skin_workspace_size(V, J):
+def size_query(abi, name, *args):
+    """A host-side ``name(args..., uint64_t* out)`` query of ``abi``: the size as an int."""
     out = _U64()
-    SKIN.check(load().exa_skin_workspace_size(V, J, ctypes.byref(out)))
+    abi.check(getattr(load(), name)(*args, ctypes.byref(out)))
     return int(out.value)
+
+
+def sizes_query(abi, name, struct, *args):
+    """A host-side ``name(args..., struct* out)`` query of ``abi``: the filled struct."""
+    out = struct()
+    abi.check(getattr(load(), name)(*args, ctypes.byref(out)))
+    return out
+
+
+def skin_workspace_size(V, J):
+    return size_query(SKIN, 'exa_skin_workspace_size', V, J)
 
 
 def knn_workspace_size(N, P1, P2, K):
-    out = _U64()
-    KNN.check(load().exa_knn_workspace_size(N, P1, P2, K, ctypes.byref(out)))
-    return int(out.value)
+    return size_query(KNN, 'exa_knn_workspace_size', N, P1, P2, K)
 
 
 def laplacian_workspace_size(B, V, C):
-    out = _U64()
-    MESH.check(load().exa_mesh_laplacian_workspace_size(B, V, C, ctypes.byref(out)))
-    return int(out.value)
+    return size_query(MESH, 'exa_mesh_laplacian_workspace_size', B, V, C)
 
 
 def blend_workspace_size(K, N):
-    out = _U64()
-    MESH.check(load().exa_mesh_blend_workspace_size(K, N, ctypes.byref(out)))
-    return int(out.value)
+    return size_query(MESH, 'exa_mesh_blend_workspace_size', K, N)
 
 
 def mesh_workspace_sizes(N, F, H, W):
-    out = ExaMeshWorkspaceSizes()
-    MESH.check(load().exa_mesh_workspace_sizes(N, F, H, W, ctypes.byref(out)))
-    return out
+    return sizes_query(MESH, 'exa_mesh_workspace_sizes', ExaMeshWorkspaceSizes, N, F, H, W)
 
 
 def workspace_sizes(P, W, H, capacity):
-    out = ExaRasterWorkspaceSizes()
-    check(load().exa_raster_workspace_sizes(P, W, H, capacity, ctypes.byref(out)))
-    return out
+    return sizes_query(RASTER, 'exa_raster_workspace_sizes', ExaRasterWorkspaceSizes, P, W, H, capacity)
 
 
 def timing_enable(on):

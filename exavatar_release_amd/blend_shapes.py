@@ -45,7 +45,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, _workspace, need_rocm
+from ._device import _ptr, _workspace, check_no_grad, check_tensor, grad_in, launch
 
 MAX_K = 512          # EXA_MESH_BLEND_MAX_K
 MAX_OUT = 1 << 30    # outputs per table
@@ -60,10 +60,8 @@ def make_table(dirs, keep):
     what = 'make_table'
     if not isinstance(dirs, torch.Tensor) or not isinstance(keep, torch.Tensor):
         raise TypeError('%s: dirs and keep must be tensors' % what)
-    if dirs.requires_grad:
-        raise ValueError('%s: dirs is data in the reference and gets no gradient; detach it' % what)
-    if dirs.dtype != torch.float32:
-        raise ValueError('%s: dirs must be float32 (it is %s)' % (what, dirs.dtype))
+    check_no_grad(what, 'dirs', dirs)
+    check_tensor(what, 'dirs', dirs)
     if dirs.dim() != 2 or not 1 <= dirs.shape[0] <= MAX_K or dirs.shape[1] > MAX_OUT:
         raise ValueError('%s: dirs must be [K, M] with 1 <= K <= %d and M <= 2^30 (it is %s)'
                          % (what, MAX_K, tuple(dirs.shape)))
@@ -90,10 +88,8 @@ class _Blend(torch.autograd.Function):
         dev = coef.device
         out = torch.empty(M, dtype=torch.float32, device=dev)
         masked = torch.empty(M, dtype=torch.float32, device=dev) if base is not None else None
-        with torch.cuda.device(dev):
-            _lib.MESH.check(_lib.load().exa_mesh_blend_forward(
-                K, N, ld, M, _ptr(coef), _ptr(table) if N else None, _ptr(cols) if N else None, _ptr(inv), _ptr(base),
-                _ptr(out), _ptr(masked), _stream_ptr(dev)))
+        launch(_lib.MESH, 'exa_mesh_blend_forward', dev, K, N, ld, M, _ptr(coef), _ptr(table) if N else None,
+               _ptr(cols) if N else None, _ptr(inv), _ptr(base), _ptr(out), _ptr(masked))
         ctx.save_for_backward(table, cols, inv)
         if masked is None:
             return out
@@ -108,16 +104,13 @@ class _Blend(torch.autograd.Function):
         K, ld = table.shape
         N, M = cols.shape[0], inv.shape[0]
         dev = table.device
-        g_out = g_out.to(torch.float32).contiguous()
-        g_masked = g_masked.to(torch.float32).contiguous() if g_masked is not None else None
+        g_out, g_masked = grad_in(g_out), grad_in(g_masked)
         dcoef = torch.empty(K, dtype=torch.float32, device=dev) if want_coef else None
         dbase = torch.empty(M, dtype=torch.float32, device=dev) if want_base else None
         nbytes = _lib.blend_workspace_size(K, N) if want_coef else 0
         ws = _workspace(nbytes, dev) if nbytes else None
-        with torch.cuda.device(dev):
-            _lib.MESH.check(_lib.load().exa_mesh_blend_backward(
-                K, N, ld, M, _ptr(table) if N else None, _ptr(cols) if N else None, _ptr(inv), _ptr(g_out),
-                _ptr(g_masked), _ptr(ws), nbytes, _ptr(dcoef), _ptr(dbase), _stream_ptr(dev)))
+        launch(_lib.MESH, 'exa_mesh_blend_backward', dev, K, N, ld, M, _ptr(table) if N else None,
+               _ptr(cols) if N else None, _ptr(inv), _ptr(g_out), _ptr(g_masked), _ptr(ws), nbytes, _ptr(dcoef), _ptr(dbase))
         return dcoef, dbase, None, None, None
 
 
@@ -125,8 +118,7 @@ def _check_table(table, what):
     if not isinstance(table, BlendTable) or not all(isinstance(t, torch.Tensor) for t in table):
         raise TypeError('%s: table must be a BlendTable of tensors (make_table builds one)' % what)
     t, cols, inv = table
-    if t.requires_grad:
-        raise ValueError('%s: table is data in the reference and gets no gradient; detach it' % what)
+    check_no_grad(what, 'table', t)
     if t.dtype != torch.float32 or cols.dtype != torch.int32 or inv.dtype != torch.int32:
         raise ValueError('%s: table must be float32 and cols, inv int32 (they are %s, %s, %s)'
                          % (what, t.dtype, cols.dtype, inv.dtype))
@@ -141,16 +133,9 @@ def _check_table(table, what):
 def _check_inputs(coef, table, base, what):
     _check_table(table, what)
     K, M = table.table.shape[0], table.inv.shape[0]
-    for name, x in (('coef', coef), ('base', base)):
-        if x is None and name != 'coef':
-            continue
-        if not isinstance(x, torch.Tensor):
-            raise TypeError('%s: %s must be a tensor' % (what, name))
-        need_rocm(x.device, what)
-        if x.dtype != torch.float32:
-            raise ValueError('%s: %s must be float32 (it is %s)' % (what, name, x.dtype))
-        if x.device != coef.device:
-            raise ValueError('%s: %s is not on the device of coef' % (what, name))
+    check_tensor(what, 'coef', coef, rocm=True)
+    if base is not None:
+        check_tensor(what, 'base', base, rocm=True, on=(coef, 'coef'))
     for name, x in zip(BlendTable._fields, table):
         if x.device != coef.device:
             raise ValueError('%s: the table (%s) is not on the device of coef; move the module with .to()' % (what, name))
@@ -178,17 +163,14 @@ class BlendShapes(nn.Module):
         super(BlendShapes, self).__init__()
         what = 'BlendShapes'
         for name, x in (('pose_dirs', pose_dirs), ('expr_dirs', expr_dirs), ('pose_mask', pose_mask)):
-            if not isinstance(x, torch.Tensor):
-                raise TypeError('%s: %s must be a tensor' % (what, name))
-            if x.requires_grad:
-                raise ValueError('%s: %s is data in the reference and gets no gradient; detach it' % (what, name))
+            check_tensor(what, name, x, f32=False)
+            check_no_grad(what, name, x)
         if pose_mask.dtype != torch.bool or pose_mask.dim() != 1:
             raise ValueError('%s: pose_mask must be a bool tensor of shape [V] (it is %s %s)'
                              % (what, pose_mask.dtype, tuple(pose_mask.shape)))
         V = pose_mask.shape[0]
-        for name, x in (('pose_dirs', pose_dirs), ('expr_dirs', expr_dirs)):
-            if x.dtype != torch.float32:
-                raise ValueError('%s: %s must be float32 (it is %s)' % (what, name, x.dtype))
+        check_tensor(what, 'pose_dirs', pose_dirs)
+        check_tensor(what, 'expr_dirs', expr_dirs)
         if pose_dirs.dim() != 2 or pose_dirs.shape[1] != 3 * V or not 1 <= pose_dirs.shape[0] <= MAX_K:
             raise ValueError('%s: pose_dirs must be [Kp, 3 V] with V = %d and 1 <= Kp <= %d (it is %s)'
                              % (what, V, MAX_K, tuple(pose_dirs.shape)))
@@ -229,7 +211,6 @@ class BlendShapes(nn.Module):
         """``module.py:537``: ``expr`` [Ke] -> ``(expr[None, None, :] * expr_dirs).sum(2)`` [V, 3], ``+0.0`` at the
         vertices whose ``expr_dirs`` row is zero; ``dL/d expr`` through the fixed two-level sum."""
         what = 'BlendShapes.expr_offsets'
-        if not isinstance(expr, torch.Tensor):
-            raise TypeError('%s: expr must be a tensor' % what)
+        check_tensor(what, 'expr', expr, f32=False)
         coef, _ = _check_inputs(expr, self.expr_plan, None, what)
         return _Blend.apply(coef, None, *self.expr_plan).view(self.vertex_num, 3)

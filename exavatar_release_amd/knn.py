@@ -31,7 +31,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, _workspace, config, need_rocm
+from ._device import _ptr, _workspace, config, grad_in, launch, need_rocm
 
 KNN = namedtuple('KNN', 'dists idx knn')
 
@@ -52,9 +52,8 @@ class _KnnPoints(torch.autograd.Function):
             flags = 0 if config.knn_cull else _lib.KNN_NO_CULL
             nbytes = _lib.knn_workspace_size(N, P1, P2, K) if config.knn_cull else 0
             ws = _workspace(nbytes, device)
-            with torch.cuda.device(device):
-                _lib.KNN.check(_lib.load().exa_knn_forward(N, P1, P2, K, _ptr(p1), _ptr(p2), flags, _ptr(ws), nbytes,
-                                                           _ptr(dists), _ptr(idx), None, _stream_ptr(device)))
+            launch(_lib.KNN, 'exa_knn_forward', device, N, P1, P2, K, _ptr(p1), _ptr(p2), flags, _ptr(ws), nbytes,
+                   _ptr(dists), _ptr(idx), None)
         if want_nn:
             knn = torch.gather(p2, 1, idx.view(N, P1 * K, 1).expand(N, P1 * K, 3)).view(N, P1, K, 3)
         else:
@@ -72,19 +71,15 @@ class _KnnPoints(torch.autograd.Function):
         if grad_dists is None and grad_knn is None:
             return None, None, None, None
         N, P1, P2, K = p1.shape[0], p1.shape[1], p2.shape[1], ctx.K
-        f32 = lambda x: None if x is None else x.to(torch.float32).contiguous()      # noqa: E731
-        grad_dists, grad_knn = f32(grad_dists), f32(grad_knn)
+        grad_dists, grad_knn = grad_in(grad_dists), grad_in(grad_knn)
         if K == 0:                                   # no refs: nothing was chosen
             return torch.zeros_like(p1), torch.zeros_like(p2), None, None
         grad_p1 = torch.empty_like(p1)
         grad_p2 = torch.empty_like(p2)
         if N * (P1 + P2) > 0:
             sorted_idx, order = torch.sort(idx.view(N, P1 * K), dim=1, stable=True)
-            with torch.cuda.device(p1.device):
-                _lib.KNN.check(_lib.load().exa_knn_backward(N, P1, P2, K, _ptr(p1), _ptr(p2), _ptr(idx),
-                                                            _ptr(grad_dists), _ptr(grad_knn), _ptr(sorted_idx),
-                                                            _ptr(order), _ptr(grad_p1), _ptr(grad_p2),
-                                                            _stream_ptr(p1.device)))
+            launch(_lib.KNN, 'exa_knn_backward', p1.device, N, P1, P2, K, _ptr(p1), _ptr(p2), _ptr(idx),
+                   _ptr(grad_dists), _ptr(grad_knn), _ptr(sorted_idx), _ptr(order), _ptr(grad_p1), _ptr(grad_p2))
         return grad_p1, grad_p2, None, None
 
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, need_rocm
+from ._device import _ptr, launch, need_rocm
 
 
 def _crop_window(bbox, img_height, img_width):
@@ -49,7 +49,6 @@ def _dev_f32(t, device, name):
 class _L1Map(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img_out, img_target, mask, bg, crop):
-        lib = _lib.load()
         device = img_out.device
         need_rocm(device, 'RGBLoss')
         if img_out.dim() != 4 or img_out.shape != img_target.shape:
@@ -60,29 +59,24 @@ class _L1Map(torch.autograd.Function):
         m = _dev_f32(mask, device, 'mask').expand(B, 1, H, W).contiguous() if compose else None
         b = _dev_f32(bg, device, 'bg').expand(B, C).contiguous() if compose else None
         out = torch.empty((B, C, crop[3], crop[2]), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _lib.check(lib.exa_l1_forward(B, C, H, W, _c_crop(crop), _ptr(x), _ptr(y), _ptr(m), _ptr(b), _ptr(out),
-                                          _stream_ptr(device)))
+        launch(_lib.RASTER, 'exa_l1_forward', device, B, C, H, W, _c_crop(crop), _ptr(x), _ptr(y), _ptr(m), _ptr(b), _ptr(out))
         ctx.crop = crop
         ctx.full = crop == (0, 0, W, H)
-        ctx.save_for_backward(x, y, m if compose else x.new_empty(0), b if compose else x.new_empty(0))
-        ctx.compose = compose
+        ctx.save_for_backward(x, y, m, b)      # (m and b are None together, without a composed target: saved as None)
         return out
 
     @staticmethod
     def backward(ctx, grad_map):
-        lib = _lib.load()
         x, y, m, b = ctx.saved_tensors
         B, C, H, W = x.shape
         g = grad_map.to(torch.float32).expand(B, C, ctx.crop[3], ctx.crop[2]).contiguous()
         dx = torch.empty_like(x) if ctx.full else torch.zeros_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.exa_l1_backward(B, C, H, W, _c_crop(ctx.crop), _ptr(x), _ptr(y), _ptr(m if ctx.compose else None),
-                                           _ptr(b if ctx.compose else None), _ptr(g), _ptr(dx), _stream_ptr(x.device)))
+        launch(_lib.RASTER, 'exa_l1_backward', x.device, B, C, H, W, _c_crop(ctx.crop), _ptr(x), _ptr(y), _ptr(m), _ptr(b),
+               _ptr(g), _ptr(dx))
         # d|x - t|/dt = -d|x - t|/dx; with a composed target t = y * mask + ..., dt/dy = mask
         dy = None
         if ctx.needs_input_grad[1]:
-            dy = -dx * m if ctx.compose else -dx
+            dy = -dx * m if m is not None else -dx
         return dx if ctx.needs_input_grad[0] else None, dy, None, None, None
 
 
@@ -100,7 +94,6 @@ class RGBLoss(nn.Module):
 class _FusedSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img_out, img_target):
-        lib = _lib.load()
         device = img_out.device
         need_rocm(device, 'the fused SSIM')
         x = img_out.detach().to(torch.float32).contiguous()
@@ -112,36 +105,32 @@ class _FusedSSIM(torch.autograd.Function):
         need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         out = torch.empty_like(x)
         maps_x = [torch.empty_like(x) for _ in range(3)] if need_x else [None, None, None]
-        with torch.cuda.device(device):
-            _lib.check(lib.exa_ssim_forward(B * C, H, W, _ptr(x), _ptr(y), _ptr(out), _ptr(maps_x[0]), _ptr(maps_x[1]),
-                                            _ptr(maps_x[2]), _stream_ptr(device)))
-            maps_y = [None, None, None]
-            if need_y:        # SSIM is symmetric: the target's derivative maps are those of ssim(y, x)
-                maps_y = [torch.empty_like(x) for _ in range(3)]
-                scratch = torch.empty_like(x)
-                _lib.check(lib.exa_ssim_forward(B * C, H, W, _ptr(y), _ptr(x), _ptr(scratch), _ptr(maps_y[0]),
-                                                _ptr(maps_y[1]), _ptr(maps_y[2]), _stream_ptr(device)))
+        launch(_lib.RASTER, 'exa_ssim_forward', device, B * C, H, W, _ptr(x), _ptr(y), _ptr(out), _ptr(maps_x[0]),
+               _ptr(maps_x[1]), _ptr(maps_x[2]))
+        maps_y = [None, None, None]
+        if need_y:        # SSIM is symmetric: the target's derivative maps are those of ssim(y, x)
+            maps_y = [torch.empty_like(x) for _ in range(3)]
+            scratch = torch.empty_like(x)
+            launch(_lib.RASTER, 'exa_ssim_forward', device, B * C, H, W, _ptr(y), _ptr(x), _ptr(scratch), _ptr(maps_y[0]),
+                   _ptr(maps_y[1]), _ptr(maps_y[2]))
         ctx.need = (need_x, need_y)
-        e = x.new_empty(0)
-        ctx.save_for_backward(x, y, *[m if m is not None else e for m in maps_x + maps_y])
+        ctx.save_for_backward(x, y, *maps_x, *maps_y)      # (the maps of a side that needs no gradient are None)
         return out
 
     @staticmethod
     def backward(ctx, grad_map):
-        lib = _lib.load()
         x, y, a0, a1, a2, b0, b1, b2 = ctx.saved_tensors
         B, C, H, W = x.shape
         g = grad_map.to(torch.float32).expand(x.shape).contiguous()
         dx = dy = None
-        with torch.cuda.device(x.device):
-            if ctx.need[0]:
-                dx = torch.empty_like(x)
-                _lib.check(lib.exa_ssim_backward(B * C, H, W, _ptr(x), _ptr(y), _ptr(g), _ptr(a0), _ptr(a1), _ptr(a2),
-                                                 _ptr(dx), _stream_ptr(x.device)))
-            if ctx.need[1]:
-                dy = torch.empty_like(x)
-                _lib.check(lib.exa_ssim_backward(B * C, H, W, _ptr(y), _ptr(x), _ptr(g), _ptr(b0), _ptr(b1), _ptr(b2),
-                                                 _ptr(dy), _stream_ptr(x.device)))
+        if ctx.need[0]:
+            dx = torch.empty_like(x)
+            launch(_lib.RASTER, 'exa_ssim_backward', x.device, B * C, H, W, _ptr(x), _ptr(y), _ptr(g), _ptr(a0), _ptr(a1),
+                   _ptr(a2), _ptr(dx))
+        if ctx.need[1]:
+            dy = torch.empty_like(x)
+            launch(_lib.RASTER, 'exa_ssim_backward', x.device, B * C, H, W, _ptr(y), _ptr(x), _ptr(g), _ptr(b0), _ptr(b1),
+                   _ptr(b2), _ptr(dy))
         return dx, dy
 
 
@@ -185,14 +174,13 @@ class _Photometric(torch.autograd.Function):
         partials = torch.empty((nblk, 2), dtype=torch.float32, device=device)
         full = crop == (0, 0, W, H)
         dimg = torch.empty_like(x) if full else torch.zeros_like(x)
-        with torch.cuda.device(device):
-            st, cc = _stream_ptr(device), _c_crop(crop)
-            _lib.check(lib.exa_photo_loss_forward(B, C, H, W, cc, _ptr(x), _ptr(y), _ptr(lw), _ptr(sm), _ptr(maps),
-                                                  _ptr(partials), st))
-            need = ctx.needs_input_grad[0]
-            if need:
-                _lib.check(lib.exa_photo_loss_grad(B, C, H, W, cc, _ptr(x), _ptr(y), _ptr(lw), _ptr(sm), float(w_l1),
-                                                   float(w_ssim), _ptr(maps), _ptr(dimg), st))
+        cc = _c_crop(crop)
+        launch(_lib.RASTER, 'exa_photo_loss_forward', device, B, C, H, W, cc, _ptr(x), _ptr(y), _ptr(lw), _ptr(sm),
+               _ptr(maps), _ptr(partials))
+        need = ctx.needs_input_grad[0]
+        if need:
+            launch(_lib.RASTER, 'exa_photo_loss_grad', device, B, C, H, W, cc, _ptr(x), _ptr(y), _ptr(lw), _ptr(sm),
+                   float(w_l1), float(w_ssim), _ptr(maps), _ptr(dimg))
         sums = partials.sum(0)                                   # [sum ssim, sum l1]
         l1_mean, ssim_mean = sums[1] / n, sums[0] / n
         loss = w_l1 * l1_mean + w_ssim * (1.0 - ssim_mean)

@@ -79,7 +79,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, need_rocm
+from ._device import _ptr, grad_in, launch, need_rocm
 
 Fragments = collections.namedtuple('Fragments', ['pix_to_face', 'zbuf', 'bary_coords', 'dists'])
 Fragments.__doc__ = """pytorch3d ``Fragments`` of one face per pixel: ``pix_to_face`` [N,H,W,1] int64 (packed n * F + f, -1 for
@@ -129,7 +129,6 @@ def _texture(texture, face_uvs):
 
 
 def _forward(verts, topo, focal, princpt, H, W, texture, face_uvs, want_zbary):
-    lib = _lib.load()
     device = verts.device
     N = verts.shape[0]
     faces = topo[0]
@@ -143,15 +142,12 @@ def _forward(verts, topo, focal, princpt, H, W, texture, face_uvs, want_zbary):
     render = torch.empty((N, texture.shape[1], H, W), dtype=torch.float32, device=device) if texture is not None else None
     g = _geometry(verts, faces, focal, princpt, H, W)
     t = _texture(texture, face_uvs)
-    with torch.cuda.device(device):
-        _lib.MESH.check(lib.exa_mesh_forward(ctypes.byref(g), ctypes.byref(t) if t is not None else None,
-                                             _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), _ptr(zbuf), _ptr(bary),
-                                             _ptr(render), _stream_ptr(device)))
+    launch(_lib.MESH, 'exa_mesh_forward', device, ctypes.byref(g), ctypes.byref(t) if t is not None else None,
+           _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), _ptr(zbuf), _ptr(bary), _ptr(render))
     return face_ws, pix_to_face, zbuf, bary, render
 
 
 def _backward(ctx, dzbuf, dbary, drender):
-    lib = _lib.load()
     verts, focal, princpt, face_ws, pix_to_face = ctx.saved_tensors[:5]
     texture, face_uvs = (ctx.saved_tensors[5], ctx.saved_tensors[6]) if ctx.textured else (None, None)
     faces, offsets, entries = ctx.topo
@@ -162,12 +158,10 @@ def _backward(ctx, dzbuf, dbary, drender):
     dverts = torch.empty_like(verts)
     g = _geometry(verts, faces, focal, princpt, ctx.H, ctx.W)
     t = _texture(texture, face_uvs)
-    f32 = lambda x: None if x is None else x.to(torch.float32).contiguous()      # noqa: E731
-    dzbuf, dbary, drender = f32(dzbuf), f32(dbary), f32(drender)
-    with torch.cuda.device(device):
-        _lib.MESH.check(lib.exa_mesh_backward(ctypes.byref(g), ctypes.byref(t) if t is not None else None, _ptr(face_ws),
-                                              _ptr(pix_to_face), _ptr(dzbuf), _ptr(dbary), _ptr(drender), _ptr(offsets),
-                                              _ptr(entries), _ptr(grad_ws), _ptr(dverts), _stream_ptr(device)))
+    dzbuf, dbary, drender = grad_in(dzbuf), grad_in(dbary), grad_in(drender)
+    launch(_lib.MESH, 'exa_mesh_backward', device, ctypes.byref(g), ctypes.byref(t) if t is not None else None,
+           _ptr(face_ws), _ptr(pix_to_face), _ptr(dzbuf), _ptr(dbary), _ptr(drender), _ptr(offsets), _ptr(entries),
+           _ptr(grad_ws), _ptr(dverts))
     return dverts
 
 
@@ -274,9 +268,7 @@ def _vertex_normals(verts, topo):
     normals = torch.empty_like(verts)
     g = _lib.ExaMeshGeometry(verts.shape[0], verts.shape[1], faces.shape[0], 0, 0, verts.data_ptr(), faces.data_ptr(),
                              None, None)
-    with torch.cuda.device(verts.device):
-        _lib.MESH.check(_lib.load().exa_mesh_vertex_normals(ctypes.byref(g), _ptr(offsets), _ptr(entries), _ptr(normals),
-                                                            _stream_ptr(verts.device)))
+    launch(_lib.MESH, 'exa_mesh_vertex_normals', verts.device, ctypes.byref(g), _ptr(offsets), _ptr(entries), _ptr(normals))
     return normals
 
 
@@ -344,10 +336,8 @@ def shade_mesh(mesh, face, cam_param, render_shape, *, light_location=(0.0, -1.0
     image = torch.empty((N, H, W, 3), dtype=torch.float32, device=device)
     pix_to_face = torch.empty((N, H, W), dtype=torch.int64, device=device)
     g = _geometry(verts, faces, focal, princpt, H, W)
-    with torch.cuda.device(device):
-        _lib.MESH.check(_lib.load().exa_mesh_forward_shaded(ctypes.byref(g), ctypes.byref(sh), _ptr(normals),
-                                                            _ptr(face_ws), _ptr(bin_ws), _ptr(pix_to_face), None,
-                                                            _ptr(image), _stream_ptr(device)))
+    launch(_lib.MESH, 'exa_mesh_forward_shaded', device, ctypes.byref(g), ctypes.byref(sh), _ptr(normals), _ptr(face_ws),
+           _ptr(bin_ws), _ptr(pix_to_face), None, _ptr(image))
     return image, pix_to_face
 
 

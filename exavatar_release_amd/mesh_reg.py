@@ -37,7 +37,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, _workspace, need_rocm
+from ._device import _ptr, _workspace, check_no_grad, check_tensor, grad_in, launch
 
 MAX_CHANNELS = 8          # EXA_MESH_LAP_MAX_CHANNELS
 MAX_NEIGHBORS = 16        # EXA_MESH_LAP_MAX_NEIGHBORS
@@ -96,12 +96,9 @@ class _Laplacian(torch.autograd.Function):
         K = idx.shape[1]
         dev = out.device
         loss, d = torch.empty_like(out), torch.empty_like(out)
-        with torch.cuda.device(dev):
-            _lib.MESH.check(_lib.load().exa_mesh_laplacian_forward(
-                B, target.shape[0] if target is not None else 1, V, C, K, _ptr(out), _ptr(target), _ptr(idx), _ptr(w),
-                _ptr(weight), _ptr(loss), _ptr(d), _stream_ptr(dev)))
-        ctx.has_weight = weight is not None
-        ctx.save_for_backward(d, w, offsets, entries, weight if weight is not None else w.new_empty(0))
+        launch(_lib.MESH, 'exa_mesh_laplacian_forward', dev, B, target.shape[0] if target is not None else 1, V, C, K,
+               _ptr(out), _ptr(target), _ptr(idx), _ptr(w), _ptr(weight), _ptr(loss), _ptr(d))
+        ctx.save_for_backward(d, w, offsets, entries, weight)      # (weight may be None: saved as None)
         ctx.mark_non_differentiable(d)
         return loss, d
 
@@ -110,35 +107,24 @@ class _Laplacian(torch.autograd.Function):
         if grad_loss is None or not ctx.needs_input_grad[0]:
             return (None,) * 7
         d, w, offsets, entries, weight = ctx.saved_tensors
-        weight = weight if ctx.has_weight else None
         B, V, C = d.shape
         dev = d.device
-        grad_loss = grad_loss.to(torch.float32).contiguous()
+        grad_loss = grad_in(grad_loss)
         gout = torch.empty_like(d)
         nbytes = _lib.laplacian_workspace_size(B, V, C)
         ws = _workspace(nbytes, dev)
-        with torch.cuda.device(dev):
-            _lib.MESH.check(_lib.load().exa_mesh_laplacian_backward(
-                B, V, C, w.shape[1], _ptr(d), _ptr(grad_loss), _ptr(w), _ptr(weight), _ptr(offsets), _ptr(entries),
-                _ptr(ws) if nbytes else None, nbytes, _ptr(gout), _stream_ptr(dev)))
+        launch(_lib.MESH, 'exa_mesh_laplacian_backward', dev, B, V, C, w.shape[1], _ptr(d), _ptr(grad_loss), _ptr(w),
+               _ptr(weight), _ptr(offsets), _ptr(entries), _ptr(ws) if nbytes else None, nbytes, _ptr(gout))
         return (gout,) + (None,) * 6
 
 
 def _check_inputs(out, target, weight, V, what):
-    for name, x in (('out', out), ('target', target), ('weight', weight)):
-        if x is None and name != 'out':
-            continue
-        if not isinstance(x, torch.Tensor):
-            raise TypeError('%s: %s must be a tensor' % (what, name))
-        need_rocm(x.device, what)
-        if x.dtype != torch.float32:
-            raise ValueError('%s: %s must be float32 (it is %s)' % (what, name, x.dtype))
-        if x.device != out.device:
-            raise ValueError('%s: %s is not on the device of out' % (what, name))
-    # what the reference holds as data gets no gradient
+    check_tensor(what, 'out', out, rocm=True)
     for name, x in (('target', target), ('weight', weight)):
-        if x is not None and x.requires_grad:
-            raise ValueError('%s: %s is data in the reference and gets no gradient; detach it' % (what, name))
+        if x is not None:
+            check_tensor(what, name, x, rocm=True, on=(out, 'out'))
+    check_no_grad(what, 'target', target)
+    check_no_grad(what, 'weight', weight)
     if out.dim() != 3 or out.shape[1] != V or not 1 <= out.shape[2] <= MAX_CHANNELS:
         raise ValueError('%s: out must be [B, V, C] with V = %d and 1 <= C <= %d (it is %s)'
                          % (what, V, MAX_CHANNELS, tuple(out.shape)))
@@ -167,8 +153,7 @@ def mesh_laplacian_loss(out, target, neighbor_idxs, neighbor_weights, weight=Non
             or neighbor_idxs.dtype not in (torch.int32, torch.int64) or not 1 <= neighbor_idxs.shape[1] <= MAX_NEIGHBORS:
         raise ValueError('%s: neighbor_idxs (int32 / int64) and neighbor_weights must be [V, K] tensors, 1 <= K <= %d'
                          % (what, MAX_NEIGHBORS))
-    if neighbor_weights.requires_grad:
-        raise ValueError('%s: neighbor_weights is data in the reference and gets no gradient; detach it' % what)
+    check_no_grad(what, 'neighbor_weights', neighbor_weights)
     out, target, weight = _check_inputs(out, target, weight, neighbor_idxs.shape[0], what)
     key = (id(neighbor_idxs), id(neighbor_weights), neighbor_idxs._version, neighbor_weights._version,
            neighbor_idxs.data_ptr(), neighbor_weights.data_ptr(), str(out.device))

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _stream_ptr, _workspace
+from ._device import _addr, _ptrs, _workspace, check_tensor, grad_in, launch
 from ._lib import ExaMlpNet
 
 HIDDEN = 128              # EXA_MLP_HIDDEN
@@ -128,46 +128,32 @@ class _MLP(torch.autograd.Function):
         dev = x.device
         net = _net(layers, hs, K0, S, W0, Ws, p, Wh, bh, trunk)
         outs = [torch.empty((N, hd.out_features), dtype=torch.float32, device=dev) for hd in hs]
-        with torch.cuda.device(dev):
-            _lib.MLP.check(_lib.load().exa_mlp_forward(ctypes.byref(net), N, x.data_ptr() if N else None,
-                                                       (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs]),
-                                                       _stream_ptr(dev)))
+        launch(_lib.MLP, 'exa_mlp_forward', dev, ctypes.byref(net), N, x.data_ptr() if N else None, _ptrs(outs))
         ctx.meta = meta
-        ctx.has_p = p is not None
-        e = x.new_empty(0)
-        ctx.save_for_backward(x, p if p is not None else e, W0, Ws if Ws is not None else e, Wh, bh, *trunk)
+        ctx.save_for_backward(x, p, W0, Ws, Wh, bh, *trunk)      # (p and Ws are None together: saved as None)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
         x, p, W0, Ws, Wh, bh, *trunk = ctx.saved_tensors
         layers, hs = ctx.meta
-        if not ctx.has_p:
-            p = Ws = None
         N, K0 = x.shape
         S = 0 if p is None else p.shape[0]
         dev = x.device
         need = ctx.needs_input_grad
         net = _net(layers, hs, K0, S, W0, Ws, p, Wh, bh, trunk)
-        gouts = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+        gouts = [grad_in(g) for g in grads]
         gx = torch.empty((N, K0), dtype=torch.float32, device=dev) if need[1] else None
         want_params = need[3] or need[5] or need[6] or any(need[7:])
         count = ctypes.c_int64()
         _lib.MLP.check(_lib.load().exa_mlp_param_count(ctypes.byref(net), ctypes.byref(count)))
         gp = torch.empty(int(count.value), dtype=torch.float32, device=dev) if want_params else None
         gws = torch.empty((HIDDEN, S), dtype=torch.float32, device=dev) if (S and need[4]) else None
-        nbytes = ctypes.c_uint64()
-        _lib.MLP.check(_lib.load().exa_mlp_workspace_size(ctypes.byref(net), N, ctypes.byref(nbytes)))
-        nbytes = int(nbytes.value)
+        nbytes = _lib.size_query(_lib.MLP, 'exa_mlp_workspace_size', ctypes.byref(net), N)
         ws = _workspace(nbytes, dev) if nbytes and (gx is not None or gp is not None or gws is not None) else None
         if gx is not None or gp is not None or gws is not None:
-            with torch.cuda.device(dev):
-                _lib.MLP.check(_lib.load().exa_mlp_backward(
-                    ctypes.byref(net), N, x.data_ptr() if N else None,
-                    (ctypes.c_void_p * len(gouts))(*[g.data_ptr() if g is not None else None for g in gouts]),
-                    gx.data_ptr() if gx is not None and N else None, gp.data_ptr() if gp is not None else None,
-                    gws.data_ptr() if gws is not None else None, ws.data_ptr() if ws is not None else None, nbytes,
-                    _stream_ptr(dev)))
+            launch(_lib.MLP, 'exa_mlp_backward', dev, ctypes.byref(net), N, x.data_ptr() if N else None, _ptrs(gouts),
+                   _addr(gx) if N else None, _addr(gp), _addr(gws), _addr(ws), nbytes)
         g_trunk = [None] * len(trunk)
         gW0 = gWh = gbh = None
         if gp is not None:
@@ -187,16 +173,6 @@ class _MLP(torch.autograd.Function):
             gWh = gp[off:off + nh * H].view(nh, H)
             gbh = gp[off + nh * H:off + nh * H + nh]
         return (None, gx, None, gW0, gws, gWh, gbh) + tuple(g_trunk)
-
-
-def _check_tensor(x, what):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError('FusedMLP: %s must be a tensor' % what)
-    if x.dtype != torch.float32:
-        raise ValueError('FusedMLP: %s must be float32 (it is %s)' % (what, x.dtype))
-    if x.device.type != 'cuda':
-        raise RuntimeError('exavatar_release_amd: FusedMLP runs on a ROCm device only (no CPU path); %s is on %s'
-                           % (what, x.device))
 
 
 def _columns(W, segs):
@@ -229,7 +205,10 @@ class FusedMLP:
         if not blocks:
             raise ValueError('FusedMLP: give at least one input block')
         for k, x in enumerate(blocks):
-            _check_tensor(x, 'input block %d' % k)
+            check_tensor('FusedMLP', 'input block %d' % k, x)
+            if x.device.type != 'cuda':      # (need_rocm's message, and which block it is)
+                raise RuntimeError('exavatar_release_amd: FusedMLP runs on a ROCm device only (no CPU path); input block %d '
+                                   'is on %s' % (k, x.device))
             if x.dim() not in (1, 2):
                 raise ValueError('FusedMLP: input block %d must be [N, c] or [c] (it is %s)' % (k, tuple(x.shape)))
         N = max([x.shape[0] for x in blocks if x.dim() == 2], default=None)
@@ -240,8 +219,7 @@ class FusedMLP:
         rows, shared, col = [], [], 0
         for k, x in enumerate(blocks):
             is_shared = x.dim() == 1 or (x.shape[0] == 1 and N != 1)
-            if x.device != dev:
-                raise ValueError('FusedMLP: input block %d is not on the device of the weights' % k)
+            check_tensor('FusedMLP', 'input block %d' % k, x, f32=False, on=(lin0.weight, 'the weights'))
             c = x.shape[-1]
             if is_shared:
                 if x.requires_grad:

@@ -55,7 +55,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _addr, _ptr, _stream_ptr, _workspace, config
+from ._device import _addr, _on_device, _ptr, _stream_ptr, _workspace, config
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -121,23 +121,6 @@ def _f32c(t, name, device, memo=None):
     if memo is not None:
         memo[id(t)] = (t, c)
     return c
-
-
-class _NoCtx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_CTX = _NoCtx()
-
-
-def _on_device(device):
-    """``torch.cuda.device(device)`` only when it is not the current device already (the context manager costs ~10 us
-    per entry, twice per render, in an eager training loop)."""
-    return _NO_CTX if torch.cuda.current_device() == device.index else torch.cuda.device(device)
 
 
 _settings_cache = []      # most recent first: (key, struct, keep); the keep list pins the tensors the key's ids name

@@ -31,7 +31,7 @@ is torch's and synchronises on ROCm, so a call with ``R`` cannot be captured; on
 import torch
 
 from . import _lib
-from ._device import _ptr, _ptrs, _stream_ptr, _workspace, need_rocm
+from ._device import _ptr, _ptrs, _workspace, check_no_grad, check_tensor, grad_in, launch
 
 MAX_JOINTS = 64           # EXA_SKIN_MAX_JOINTS
 MAX_SETS = 4              # EXA_SKIN_MAX_SETS
@@ -46,46 +46,27 @@ class _Skin(torch.autograd.Function):
         V, S, J, Vw = points[0].shape[0], len(points), T.shape[0], weights.shape[0]
         dev = T.device
         outs = [torch.empty((V, 3), dtype=torch.float32, device=dev) for _ in points]
-        with torch.cuda.device(dev):
-            _lib.SKIN.check(_lib.load().exa_skin_forward(V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T),
-                                                         _ptr(trans), _ptr(Rinv), _ptr(t), _ptrs(outs),
-                                                         _stream_ptr(dev)))
-        ctx.has_idx = idx is not None
-        ctx.has_cam = Rinv is not None
-        ctx.save_for_backward(weights, idx if idx is not None else weights.new_empty(0),
-                              Rinv if Rinv is not None else weights.new_empty(0), T, *points)
+        launch(_lib.SKIN, 'exa_skin_forward', dev, V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T),
+               _ptr(trans), _ptr(Rinv), _ptr(t), _ptrs(outs))
+        ctx.save_for_backward(weights, idx, Rinv, T, *points)      # (idx and Rinv may be None: saved as None)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
         weights, idx, Rinv, T, *points = ctx.saved_tensors
-        idx = idx if ctx.has_idx else None
-        Rinv = Rinv if ctx.has_cam else None
         V, S, J, Vw = points[0].shape[0], len(points), T.shape[0], weights.shape[0]
         dev = T.device
         need = ctx.needs_input_grad
-        grads = [torch.zeros((V, 3), dtype=torch.float32, device=dev) if g is None else g.to(torch.float32).contiguous()
-                 for g in grads]
+        grads = [torch.zeros((V, 3), dtype=torch.float32, device=dev) if g is None else grad_in(g) for g in grads]
         gpts = [torch.empty((V, 3), dtype=torch.float32, device=dev) if need[6 + s] else None for s in range(S)]
         gT = torch.empty((J, 4, 4), dtype=torch.float32, device=dev) if need[4] else None
         gtrans = torch.empty(3, dtype=torch.float32, device=dev) if need[5] else None
         if any(g is not None for g in gpts) or gT is not None or gtrans is not None:
             nbytes = _lib.skin_workspace_size(V, J)
             ws = _workspace(nbytes, dev)
-            with torch.cuda.device(dev):
-                _lib.SKIN.check(_lib.load().exa_skin_backward(
-                    V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T), _ptr(Rinv), _ptrs(grads),
-                    _ptrs(gpts), _ptr(gT), _ptr(gtrans), _ptr(ws) if nbytes else None, nbytes, _stream_ptr(dev)))
+            launch(_lib.SKIN, 'exa_skin_backward', dev, V, S, J, Vw, _ptrs(points), _ptr(weights), _ptr(idx), _ptr(T),
+                   _ptr(Rinv), _ptrs(grads), _ptrs(gpts), _ptr(gT), _ptr(gtrans), _ptr(ws) if nbytes else None, nbytes)
         return (None, None, None, None, gT, gtrans) + tuple(gpts)
-
-
-def _check_f32(x, name, shape=None):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError('skin_points: %s must be a tensor' % name)
-    if x.dtype != torch.float32:
-        raise ValueError('skin_points: %s must be float32 (it is %s)' % (name, x.dtype))
-    if shape is not None and tuple(x.shape) != tuple(shape):
-        raise ValueError('skin_points: %s must have shape %s (it has %s)' % (name, tuple(shape), tuple(x.shape)))
 
 
 def skin_points(points, transform_mat_joint, skinning_weight, idx=None, trans=None, R=None, t=None):
@@ -94,25 +75,25 @@ def skin_points(points, transform_mat_joint, skinning_weight, idx=None, trans=No
     ``transform_mat_joint`` [J, 4, 4] (J <= 64), ``skinning_weight`` [Vw, J], ``idx`` [V] int64 or None (then Vw == V),
     ``trans`` [3] or [1, 3] or None (zero), ``R`` [3, 3] and ``t`` [3] or [1, 3] (both or neither: the camera -> world
     step ``inverse(R) (p - t)``).  Returns a tuple with one posed ``[V, 3]`` tensor per set."""
+    what = 'skin_points'
     sets = (points,) if isinstance(points, torch.Tensor) else tuple(points)
     if not 1 <= len(sets) <= MAX_SETS:
         raise ValueError('skin_points: 1 .. %d point sets (got %d)' % (MAX_SETS, len(sets)))
     T = transform_mat_joint
     # what the reference holds as a buffer or as data gets no gradient
-    for name, x in (('skinning_weight', skinning_weight), ('R', R), ('t', t)):
-        if isinstance(x, torch.Tensor) and x.requires_grad:
-            raise ValueError('skin_points: %s is %s in the reference and gets no gradient; detach it'
-                             % (name, 'a buffer' if name == 'skinning_weight' else 'camera data'))
-    _check_f32(T, 'transform_mat_joint')
+    check_no_grad(what, 'skinning_weight', skinning_weight, 'a buffer')
+    check_no_grad(what, 'R', R, 'camera data')
+    check_no_grad(what, 't', t, 'camera data')
+    check_tensor(what, 'transform_mat_joint', T)
     if T.dim() != 3 or T.shape[1:] != (4, 4) or not 1 <= T.shape[0] <= MAX_JOINTS:
         raise ValueError('skin_points: transform_mat_joint must be [J, 4, 4] with 1 <= J <= %d' % MAX_JOINTS)
     J = T.shape[0]
     for s, x in enumerate(sets):
-        _check_f32(x, 'points[%d]' % s)
+        check_tensor(what, 'points[%d]' % s, x)
         if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] != sets[0].shape[0]:
             raise ValueError('skin_points: every point set must be [V, 3] with the same V')
     V = sets[0].shape[0]
-    _check_f32(skinning_weight, 'skinning_weight')
+    check_tensor(what, 'skinning_weight', skinning_weight)
     if skinning_weight.dim() != 2 or skinning_weight.shape[1] != J:
         raise ValueError('skin_points: skinning_weight must be [Vw, J] with J = %d' % J)
     if idx is not None:
@@ -121,24 +102,23 @@ def skin_points(points, transform_mat_joint, skinning_weight, idx=None, trans=No
     elif skinning_weight.shape[0] != V:
         raise ValueError('skin_points: without idx, skinning_weight must have V = %d rows' % V)
     if trans is not None:
-        _check_f32(trans, 'trans')
+        check_tensor(what, 'trans', trans)
         if tuple(trans.shape) not in ((3,), (1, 3)):
             raise ValueError('skin_points: trans must be [3] or [1, 3]')
     if (R is None) != (t is None):
         raise ValueError('skin_points: R and t must be given together')
     if R is not None:
-        _check_f32(R, 'R', (3, 3))
-        _check_f32(t, 't')
+        check_tensor(what, 'R', R)
+        if tuple(R.shape) != (3, 3):
+            raise ValueError('skin_points: R must have shape (3, 3) (it has %s)' % (tuple(R.shape),))
+        check_tensor(what, 't', t)
         if tuple(t.shape) not in ((3,), (1, 3)):
             raise ValueError('skin_points: t must be [3] or [1, 3]')
     dev = T.device
     for name, x in [('transform_mat_joint', T), ('skinning_weight', skinning_weight), ('idx', idx), ('trans', trans),
                     ('R', R), ('t', t)] + [('points[%d]' % s, x) for s, x in enumerate(sets)]:
-        if x is None:
-            continue
-        need_rocm(x.device, 'skin_points')
-        if x.device != dev:
-            raise ValueError('skin_points: %s is not on the device of transform_mat_joint' % name)
+        if x is not None:
+            check_tensor(what, name, x, f32=False, rocm=True, on=(T, 'transform_mat_joint'))
     if trans is None:
         trans = torch.zeros(3, dtype=torch.float32, device=dev)
     Rinv = tv = None

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import _ptr, _stream_ptr, need_rocm
+from ._device import _ptr, grad_in, launch, need_rocm
 
 BWD_BLOCK = 1024          # threads of a backward workgroup (csrc/triplane.hip)
 MAX_LDS = 65536           # EXA_TRIPLANE_MAX_LDS
@@ -107,9 +107,7 @@ class _Plan:
         N = coords.shape[0]
         keys = torch.empty(N * 12, dtype=torch.int32, device=dev)
         if N:
-            with torch.cuda.device(dev):
-                _lib.TRIPLANE.check(_lib.load().exa_triplane_plan_keys(N, H, W, _ptr(coords), _ptr(is_face_u8),
-                                                                       _ptr(keys), _stream_ptr(dev)))
+            launch(_lib.TRIPLANE, 'exa_triplane_plan_keys', dev, N, H, W, _ptr(coords), _ptr(is_face_u8), _ptr(keys))
         self.keys = keys
         for k, v in plan_tables(keys, 6 * H * W, C).items():
             setattr(self, k, v)
@@ -124,10 +122,8 @@ class _TriplaneLookup(torch.autograd.Function):
         N = tf.num_rows
         out = torch.empty((N, 3 * C), dtype=torch.float32, device=body.device)
         if N:
-            with torch.cuda.device(body.device):
-                _lib.TRIPLANE.check(_lib.load().exa_triplane_forward(N, C, H, W, _ptr(body), _ptr(face), _ptr(tf.coords),
-                                                                     _ptr(tf.is_face_u8), _ptr(out),
-                                                                     _stream_ptr(body.device)))
+            launch(_lib.TRIPLANE, 'exa_triplane_forward', body.device, N, C, H, W, _ptr(body), _ptr(face),
+                   _ptr(tf.coords), _ptr(tf.is_face_u8), _ptr(out))
         ctx.tf = tf
         ctx.shape = (C, H, W)
         return out
@@ -136,15 +132,13 @@ class _TriplaneLookup(torch.autograd.Function):
     def backward(ctx, grad_out):
         tf, (C, H, W) = ctx.tf, ctx.shape
         p = tf.plan
-        grad_out = grad_out.to(torch.float32).contiguous()
+        grad_out = grad_in(grad_out)
         dev = grad_out.device
         grad_body = torch.empty((3, C, H, W), dtype=torch.float32, device=dev)
         grad_face = torch.empty((3, C, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.TRIPLANE.check(_lib.load().exa_triplane_backward(
-                tf.num_rows, C, H, W, _ptr(tf.coords), _ptr(grad_out), _ptr(p.entries), _ptr(p.seg_entry),
-                _ptr(p.tex_seg), _ptr(p.wg_tex), p.num_wg, p.max_wg_segments, _ptr(grad_body), _ptr(grad_face),
-                _stream_ptr(dev)))
+        launch(_lib.TRIPLANE, 'exa_triplane_backward', dev, tf.num_rows, C, H, W, _ptr(tf.coords), _ptr(grad_out),
+               _ptr(p.entries), _ptr(p.seg_entry), _ptr(p.tex_seg), _ptr(p.wg_tex), p.num_wg, p.max_wg_segments,
+               _ptr(grad_body), _ptr(grad_face))
         return grad_body, grad_face, None
 
 

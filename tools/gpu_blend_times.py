@@ -17,7 +17,6 @@ Prints one JSON line; --out writes it to a file too.
     python tools/gpu_blend_times.py [--reps 7] [--iters 100] [--out blend_times.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -28,29 +27,7 @@ sys.path.insert(0, ROOT)
 
 import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import build                       # noqa: E402
-
-
-def window_ms(fn, iters):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) / iters
-
-
-def medians(fns, reps, iters, warmup=10):
-    """Median per-call milliseconds of every function, their windows interleaved."""
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            times[k].append(window_ms(fn, iters))
-    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}, {k: (min(v), max(v)) for k, v in times.items()}
+from _timing import emit, medians                           # noqa: E402
 
 
 def main():
@@ -143,12 +120,7 @@ def main():
     res['pose_dirs_bytes'] = pose_dirs.numel() * 4
     res['ref_pose_fwd_GBps_of_full_table'] = pose_dirs.numel() * 4 / (med['pose100_ref_fwd_ms'] * 1e-3) / 1e9
     res.update(checks)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

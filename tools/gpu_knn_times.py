@@ -12,7 +12,6 @@ writes it to a file too.
     python tools/gpu_knn_times.py [--reps 10] [--out knn_times.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -24,6 +23,7 @@ sys.path.insert(0, ROOT)
 import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import _lib, build, p3d_standins, scenes   # noqa: E402
 from exavatar_release_amd.rasterizer import _ptr, _stream_ptr  # noqa: E402
+from _timing import emit, median_ms                         # noqa: E402
 
 
 def shapes():
@@ -33,22 +33,6 @@ def shapes():
     xyz = torch.cat([torch.randn(150000, 3, generator=g) * 2, torch.rand(150000, 3, generator=g) * 8 - 4])
     xyz = xyz[torch.randperm(300000, generator=g)].contiguous()
     return {'k1': (q[None], refs[None], 1), 'k4': (xyz[None], xyz[None], 4)}
-
-
-def median_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        e.synchronize()
-        times.append(s.elapsed_time(e))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def visited_fraction(p1, p2, K):
@@ -100,12 +84,7 @@ def main():
         row['speedup_cull_vs_standin'] = row['standin_ms'] / row['hip_cull_ms']
         row['speedup_cull_vs_nocull'] = row['hip_nocull_ms'] / row['hip_cull_ms']
         res[name] = row
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

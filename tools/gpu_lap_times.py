@@ -17,7 +17,6 @@ JSON line; --out writes it to a file too.
     python tools/gpu_lap_times.py [--reps 7] [--iters 200] [--out lap_times.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -29,6 +28,7 @@ sys.path.insert(0, ROOT)
 
 import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import build                       # noqa: E402
+from _timing import emit, medians                           # noqa: E402
 
 
 def grid_faces(rows, cols):
@@ -50,29 +50,6 @@ class ReferenceExpression:
         if target is None:
             return self.lap(out) ** 2
         return (self.lap(out) - self.lap(target)) ** 2
-
-
-def window_ms(fn, iters):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) / iters
-
-
-def medians(fns, reps, iters, warmup=10):
-    """Median per-call milliseconds of every function, their windows interleaved."""
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            times[k].append(window_ms(fn, iters))
-    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}, {k: (min(v), max(v)) for k, v in times.items()}
 
 
 def main():
@@ -146,12 +123,7 @@ def main():
     again = torch.autograd.grad(ref(x, neutral), x, G)[0]
     res['ref_grad_elements_differing_between_two_calls'] = int((again != g_ref).sum())
     res['hip_grad_elements_differing_between_two_calls'] = int((torch.autograd.grad(hip(x, neutral), x, G)[0] != g_hip).sum())
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 
 import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import build                      # noqa: E402
+from _timing import emit, median_ms                         # noqa: E402
 
 TRI, POSE, NORMAL = 96, 126, 3
 
@@ -38,22 +39,6 @@ def trunk(widths, trailing=0):
     if trailing:
         mods.append(nn.Linear(widths[-1], trailing))
     return nn.Sequential(*mods)
-
-
-def median_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        e.synchronize()
-        times.append(s.elapsed_time(e))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def main():
@@ -136,12 +121,7 @@ def main():
             r['speedup_' + k] = r['ref_%s_ms' % k] / r['hip_%s_ms' % k]
         res['nets'][label] = r
         print(label, json.dumps(r), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

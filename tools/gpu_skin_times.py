@@ -15,7 +15,6 @@ writes it to a file too.
     python tools/gpu_skin_times.py [--reps 50] [--out skin_times.json]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -28,6 +27,7 @@ import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import _lib, build, lbs, scenes    # noqa: E402
 from exavatar_release_amd.rasterizer import _ptr, _stream_ptr, _workspace  # noqa: E402
 from exavatar_release_amd.skinning import _ptrs              # noqa: E402
+from _timing import emit, median_ms                         # noqa: E402
 
 
 def reference_expression(points, T, weights, idx, trans, R, t):
@@ -39,22 +39,6 @@ def reference_expression(points, T, weights, idx, trans, R, t):
         xyz = torch.bmm(tmv, xyz[:, :, None]).view(V, 4)[:, :3] + trans
         outs.append(torch.matmul(torch.inverse(R), (xyz - t.view(1, 3)).permute(1, 0)).permute(1, 0))
     return outs
-
-
-def median_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        e.synchronize()
-        times.append(s.elapsed_time(e))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def main():
@@ -120,12 +104,7 @@ def main():
         ours = exa.skin_points(points, T, W, idx, trans, R, t)
         ref = reference_expression(points, T, W, idx, trans, R, t)
         res['fwd_max_abs_diff_vs_ref'] = max(float((a - b).abs().max()) for a, b in zip(ours, ref))
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':

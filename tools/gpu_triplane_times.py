@@ -14,7 +14,6 @@ expression within 2e-6.  Prints one JSON line; --out writes it to a file too.
     python tools/gpu_triplane_times.py [--reps 50] [--out triplane_times.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -28,6 +27,7 @@ sys.path.insert(0, ROOT)
 import exavatar_release_amd as exa                          # noqa: E402
 from exavatar_release_amd import _lib, build, scenes         # noqa: E402
 from exavatar_release_amd.rasterizer import _ptr, _stream_ptr  # noqa: E402
+from _timing import emit, median_ms                         # noqa: E402
 
 
 def reference_expression(xyz, is_face, triplane, triplane_face, shape_3d=(2, 2, 2), face_shape_3d=(0.3, 0.3, 0.3)):
@@ -42,22 +42,6 @@ def reference_expression(xyz, is_face, triplane, triplane_face, shape_3d=(2, 2, 
     tri_feat = feats(triplane, xyz, shape_3d)
     tri_feat[is_face] = feats(triplane_face, xyz[is_face, :], face_shape_3d)
     return tri_feat
-
-
-def median_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        e.synchronize()
-        times.append(s.elapsed_time(e))
-    times.sort()
-    return times[len(times) // 2]
 
 
 def main():
@@ -108,12 +92,7 @@ def main():
         d = (tf(body, face) - reference_expression(xyz, is_face, body, face)).abs().max().item()
     res['fwd_max_abs_diff_vs_ref'] = d
     res['fwd_within_2e-6'] = bool(d <= 2e-6)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(line + '\n')
+    emit(res, args.out)
 
 
 if __name__ == '__main__':
