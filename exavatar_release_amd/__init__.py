@@ -41,6 +41,11 @@ and for the blend-shape offsets on the upsampled mesh (the pose correctives of `
 expression offsets, reference ``avatar/common/nets/module.py:473-493,537``):
 
     from exavatar_release_amd import BlendShapes
+
+and for the forward kinematics that turn the pose into ``transform_mat_joint`` (``get_transform_mat_joint`` and smplx's
+``batch_rigid_transform``, reference ``avatar/common/nets/module.py:389-411``, ``smplx/lbs.py:361-417``):
+
+    from exavatar_release_amd import joint_transforms, batch_rigid_transform
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -56,6 +61,7 @@ from .skinning import skin_points
 from .mlp import FusedMLP
 from .mesh_reg import LaplacianReg, mesh_laplacian_loss
 from .blend_shapes import BlendShapes, BlendTable, blend_offsets
+from .kinematics import batch_rigid_transform, joint_transforms
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -63,4 +69,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
-           'blend_offsets']
+           'blend_offsets', 'joint_transforms', 'batch_rigid_transform']

@@ -170,6 +170,7 @@ _GP = ctypes.POINTER(ExaMeshGeometry)
 _TP = ctypes.POINTER(ExaMeshTexture)
 _SHP = ctypes.POINTER(ExaMeshShading)
 _PP = ctypes.POINTER(c_void_p)       # host array of device pointers
+_IP = ctypes.POINTER(ctypes.c_int32)  # host array of int32
 
 # ---- the six ABIs
 # the Gaussian rasterizer with its image losses (exa_ssim_*, exa_photo_*, exa_l1_* report through exa_raster_last_error)
@@ -218,7 +219,8 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
             ExaRasterBackwardJob))
 
-# the triangle rasterizer of the face render, the mesh Laplacian regulariser and the blend-shape offsets
+# the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets and the forward
+# kinematics
 MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -239,6 +241,10 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_blend_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 8),
     'exa_mesh_blend_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
     'exa_mesh_blend_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 6 + [_U64, c_void_p, c_void_p, c_void_p]),
+    # the forward kinematics (csrc/kinematics.hip); `parents` is a host int32 array
+    'exa_mesh_kinematics_depths': (ctypes.c_int, [_I32, _IP, _IP]),
+    'exa_mesh_kinematics_forward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 8),
+    'exa_mesh_kinematics_backward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 11),
 },_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
 
 # the K-nearest-neighbour search

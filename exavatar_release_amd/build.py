@@ -49,6 +49,8 @@ SOURCES = {
     'mesh_reg.hip': ['-ffp-contract=off'],
     # the blend-shape offsets and their backward are defined operation by operation (include/exa_mesh.h)
     'blend_shapes.hip': ['-ffp-contract=off'],
+    # the forward kinematics and their backward are defined operation by operation (include/exa_mesh.h)
+    'kinematics.hip': ['-ffp-contract=off'],
 }
 
 

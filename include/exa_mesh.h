@@ -20,6 +20,9 @@
  * So do the blend-shape offsets of the same upsampled mesh: `exa_mesh_blend_*` are the reference's pose correctives and
  * expression offsets (avatar/common/nets/module.py:484-493,537) under `exavatar_release_amd.blend_shapes.BlendShapes`.
  *
+ * And the forward kinematics that feed the skinning of that mesh: `exa_mesh_kinematics_*` are the reference's
+ * `get_transform_mat_joint` (avatar/common/nets/module.py:389-411) under `exavatar_release_amd.kinematics`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -237,6 +240,79 @@ int exa_mesh_blend_workspace_size(int32_t K, int32_t N, uint64_t* out_bytes);
 int exa_mesh_blend_backward(int32_t K, int32_t N, int32_t ld, int32_t M, const float* table, const int32_t* cols,
                             const int32_t* inv, const float* g_out, const float* g_masked, void* ws, uint64_t ws_bytes,
                             float* dL_dcoef, float* dL_dbase, void* stream);
+
+/* ---- Forward kinematics (reference get_transform_mat_joint) ---------------------------------------------------------
+ * The pose -> joint-transform chain in front of the skinning: pytorch3d's `axis_angle_to_matrix`, smplx's
+ * `batch_rigid_transform` (avatar/common/utils/smplx/smplx/lbs.py:361-417) and the `bmm` with the big-pose transforms
+ * (avatar/common/nets/module.py:389-411), under `exavatar_release_amd.kinematics.joint_transforms`.  B skeletons of one
+ * tree per call, J joints (1 <= J <= EXA_MESH_KIN_MAX_JOINTS), one wave per skeleton, one launch each way, no
+ * workspace.  Like the Laplacian and the blend shapes it joins this ABI; no existing prototype changes:
+ * EXA_MESH_VERSION stays 100.
+ *
+ * `parents` is a HOST int32[J]: parents[0] == -1 and 0 <= parents[i] < i.  It is checked before any GPU work and
+ * travels to the kernel by value; the library keeps nothing between calls.  depth(0) = 0, depth(i) =
+ * depth(parents[i]) + 1.
+ *
+ * Forward.  Every operation rounded in fp32, no fused multiply-add, in exactly this order, per joint j:
+ *   1. R_j.  With `rot_in`: R_j = rot_in[j].  With `pose` = (x, y, z), pytorch3d's quaternion route:
+ *        angle = sqrt((x x + y y) + z z);  half = 0.5 angle
+ *        s = sin(half) / angle, or 0.5 - (angle angle) / 48 when angle < 1e-6
+ *        (r, i, j, k) = (cos(half), s x, s y, s z);  n = ((r r + i i) + j j) + k k;  two_s = 2 / n
+ *        R = [1 - two_s (j j + k k),  two_s (i j - k r),      two_s (i k + j r);
+ *             two_s (i j + k r),      1 - two_s (i i + k k),  two_s (j k - i r);
+ *             two_s (i k - j r),      two_s (j k + i r),      1 - two_s (i i + j j)]
+ *      sin and cos are the device library's sinf / cosf: this is the one step a CPU does not reproduce bit for bit.
+ *      R_j is written to `rot`.
+ *   2. L_j = [R_j | t_j],  t_j = joints[j] - joints[parents[j]]  (t_0 = joints[0]).
+ *   3. W_0 = L_0; then for depth 1, 2, .. (a joint after its parent p), rows r = 0 .. 2:
+ *        W_j[r][c] = (W_p[r][0] R_j[0][c] + W_p[r][1] R_j[1][c]) + W_p[r][2] R_j[2][c]            c = 0 .. 2
+ *        W_j[r][3] = ((W_p[r][0] t_j[0] + W_p[r][1] t_j[1]) + W_p[r][2] t_j[2]) + W_p[r][3]
+ *      posed_joints[j] = W_j[:, 3].
+ *   4. A_j[r][c] = W_j[r][c] (c < 3),  A_j[r][3] = W_j[r][3] - ((W_j[r][0] J_0 + W_j[r][1] J_1) + W_j[r][2] J_2) with
+ *      J = joints[j];  row 3 of A_j = (0, 0, 0, 1).
+ *   5. Without `pre`: transforms[j] = A_j.  With `pre`: rows r = 0 .. 2
+ *        transforms[j][r][c] = ((A[r][0] pre[0][c] + A[r][1] pre[1][c]) + A[r][2] pre[2][c]) + A[r][3] pre[3][c]
+ *      and row 3 = row 3 of pre[j].
+ *
+ * Backward, atomic-free and bit-deterministic.  g = grad_transforms[j] (zero when NULL), gp = grad_posed_joints[j]
+ * (zero when NULL); W is recomputed exactly as above from the saved `rot`.
+ *   GA[r][k] = g[r][k] without `pre`, else ((g[r][0] pre[k][0] + g[r][1] pre[k][1]) + g[r][2] pre[k][2]) +
+ *              g[r][3] pre[k][3]                                                       r = 0 .. 2, k = 0 .. 3
+ *   grad_pre[k][c] = (A[0][k] g[0][c] + A[1][k] g[1][c]) + A[2][k] g[2][c]  for k < 3, and
+ *   grad_pre[3][c] = ((A[0][3] g[0][c] + A[1][3] g[1][c]) + A[2][3] g[2][c]) + g[3][c]
+ *   GW_j[r][c] = GA[r][c] - GA[r][3] J_c (c < 3),  GW_j[r][3] = GA[r][3] + gp[r]         the joint's own term
+ *   rest_c = (GA[0][3] W_j[0][c] + GA[1][3] W_j[1][c]) + GA[2][3] W_j[2][c]
+ *   for depth d = deepest .. 1: every parent p of depth d - 1 adds, over its children i of depth d in ascending i,
+ *        GW_p[r][k] = GW_p[r][k] + (((GW_i[r][0] R_i[k][0] + GW_i[r][1] R_i[k][1]) + GW_i[r][2] R_i[k][2]) +
+ *                                   GW_i[r][3] t_i[k])       k < 3,       GW_p[r][3] = GW_p[r][3] + GW_i[r][3]
+ *      (GW_i is final by then: its own children were added one level earlier)
+ *   GL_j[k][c] = (W_p[0][k] GW_j[0][c] + W_p[1][k] GW_j[1][c]) + W_p[2][k] GW_j[2][c]   (GL_0 = GW_0), k < 3, c < 4
+ *   grad_rot[j] = GL_j[:, 0 .. 2]
+ *   grad_joints[j][c] = (-rest_c + GL_j[c][3]), then for the children i of j in ascending i: - GL_i[c][3]
+ *   grad_pose[j] = the analytic Jacobian of step 1 applied to grad_rot[j], with d angle / d x := 0 at angle == 0 (what
+ *      torch's `norm` gives): a zero pose row gets the finite gradient of q = (1, x / 2, y / 2, z / 2), not NaN.
+ * B == 0 is a successful no-op in every call. */
+#define EXA_MESH_KIN_MAX_JOINTS 64
+
+/* Host-only helper: validates the tree (EXA_MESH_E_INVALID with a message naming the first bad entry) and writes every
+ * joint's depth.  parents [J] and depth_out [J] are HOST memory. */
+int exa_mesh_kinematics_depths(int32_t J, const int32_t* parents, int32_t* depth_out);
+
+/* One launch.  parents HOST [J]; exactly one of pose [dev] [B, J, 3] (axis-angle) and rot_in [dev] [B, J, 3, 3];
+ * joints [dev] [B, J, 3]; pre [dev] [B, J, 4, 4] or NULL; transforms [dev] [B, J, 4, 4], posed_joints [dev] [B, J, 3]
+ * and rot [dev] [B, J, 3, 3]: all required, fully written. */
+int exa_mesh_kinematics_forward(int32_t B, int32_t J, const int32_t* parents, const float* pose, const float* rot_in,
+                                const float* joints, const float* pre, float* transforms, float* posed_joints,
+                                float* rot, void* stream);
+
+/* One launch.  pose as in the forward (read for grad_pose only, else NULL); rot [dev] the forward's output; joints, pre
+ * as in the forward; grad_transforms [dev] [B, J, 4, 4] and grad_posed_joints [dev] [B, J, 3]: either may be NULL
+ * (zero).  Outputs, each [dev], optional (NULL: not wanted) and fully written when given: grad_pose [B, J, 3] (needs
+ * pose), grad_rot [B, J, 3, 3], grad_joints [B, J, 3], grad_pre [B, J, 4, 4] (needs pre). */
+int exa_mesh_kinematics_backward(int32_t B, int32_t J, const int32_t* parents, const float* pose, const float* rot,
+                                 const float* joints, const float* pre, const float* grad_transforms,
+                                 const float* grad_posed_joints, float* grad_pose, float* grad_rot, float* grad_joints,
+                                 float* grad_pre, void* stream);
 
 #ifdef __cplusplus
 }
