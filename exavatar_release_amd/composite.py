@@ -44,14 +44,12 @@ def _compose_launch(cjobs, store_ctx, device, capturing, sorted_event=None):
         a.geom_a, a.tile_a, a.bin_a, a.capacity_a = ja.geom_ptr, ja.tile_ptr, ja.bin_ptr, ja.capacity
         a.geom_b, a.tile_b, a.bin_b, a.capacity_b = jb.geom_ptr, jb.tile_ptr, jb.bin_ptr, jb.capacity
         a.tile_ws, a.bin_ws, a.capacity = c.tile_ptr, c.bin_ptr, c.capacity
-        base = c.planes.data_ptr()
-        H, W = int(c.rs.image_height), int(c.rs.image_width)
-        a.out_color, a.out_depth, a.out_alpha = base, base + 12 * H * W, base + 16 * H * W
+        a.out_color, a.out_depth, a.out_alpha = rz._plane_ptrs(c.planes, ja.H, ja.W)      # (one image size: _Compose.forward)
         # source A's finished images: where B has no entry the composite's pixels are A's (equal backgrounds are checked on
         # the device): those sub-tiles skip merge, blend and backward (include/exa_raster.h, ExaRasterComposeJob.a_color)
         if rz.config.compose_reuse_source and ja.settings.bg:
-            pa = ja.planes.data_ptr()
-            a.a_color, a.a_depth, a.a_alpha, a.a_bg = pa, pa + 12 * H * W, pa + 16 * H * W, ja.settings.bg
+            a.a_color, a.a_depth, a.a_alpha = rz._plane_ptrs(ja.planes, ja.H, ja.W)
+            a.a_bg = ja.settings.bg
         if c.radii is not None:
             a.radii_a, a.radii_b, a.radii_out = ja.radii.data_ptr(), jb.radii.data_ptr(), c.radii.data_ptr()
             a.is_vis_a, a.is_vis_b, a.is_vis_out = ja.is_vis.data_ptr(), jb.is_vis.data_ptr(), c.is_vis.data_ptr()
@@ -134,7 +132,7 @@ class _Compose(torch.autograd.Function):
         rz._tls.is_vis = [c.is_vis for c in cjobs]
         outs = []
         for c in cjobs:
-            col, d, al = torch.split_with_sizes(c.planes, rz._PLANES)
+            col, d, al = rz._plane_outputs(c.planes)
             outs += [col, c.radii, d, al]
         if need_ctx:
             ctx.K, ctx.cjobs, ctx.device = K, cjobs, device
@@ -142,15 +140,10 @@ class _Compose(torch.autograd.Function):
                 all(c.b.token_ref is not None and c.b.token_ref() is token for c in cjobs)
             # B's converted inputs go through save_for_backward like _Rasterize's: an in-place update between the sources'
             # forward and this backward (the splat records of the sources hold the OLD values) raises instead of mixing
-            saved, empty = [], None
-            for c in cjobs:
+            saved = []
+            for c in cjobs:                 # (an input that was not given is saved, and handed back, as None)
                 jb = c.b
-                for t in (jb.means3D, jb.sh, jb.colors, jb.opac, jb.scales, jb.rot, jb.cov):
-                    if t is None:
-                        if empty is None:
-                            empty = torch.empty(0, device=device)
-                        t = empty
-                    saved.append(t)
+                saved += [jb.means3D, jb.sh, jb.colors, jb.opac, jb.scales, jb.rot, jb.cov]
             ctx.save_for_backward(*saved)
         ctx.mark_non_differentiable(*[outs[4 * k + 1] for k in range(K) if outs[4 * k + 1] is not None])
         ctx.set_materialize_grads(False)
@@ -175,44 +168,19 @@ class _Compose(torch.autograd.Function):
             for k, c in enumerate(cjobs):
                 ja, jb = c.a, c.b
                 P, H, W, sh_M = jb.P, jb.H, jb.W, jb.sh_M
-                has_sh, has_col, has_sc, has_rot, has_cov = [t is not None for t in (jb.sh, jb.colors, jb.scales, jb.rot, jb.cov)]
-                g_color = rz._grad_in(grads[4 * k], (3, H, W), device)
-                if g_color is None:
-                    g_color = torch.zeros((3, H, W), dtype=rz._F32, device=device)
-                g_depth = rz._grad_in(grads[4 * k + 2], (1, H, W), device)
-                g_alpha = rz._grad_in(grads[4 * k + 3], (1, H, W), device)
+                inputs7 = saved[7 * k: 7 * k + 7]          # B's, as its own render converted them
+                _, has_sh, has_col, _, has_sc, has_rot, has_cov = [t is not None for t in inputs7]
+                image_grads = rz._image_grads(grads[4 * k: 4 * k + 4], H, W, device)
                 nd = need[rz.N_IN * k: rz.N_IN * (k + 1)]
-                want = ((nd[0], 3), (nd[1], 3), (has_col and nd[3], 3), (nd[4], 1), (has_sc and nd[5], 3), (has_rot and nd[6], 4),
-                        (has_cov and nd[7], 6))
-                widths = [w for on, w in want if on]
-                pieces = iter(torch.split_with_sizes(torch.empty(P * sum(widths), dtype=rz._F32, device=device), [P * w for w in widths])) \
-                    if widths else iter(())
-                d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov = \
-                    [next(pieces).view(P, w) if on else None for on, w in want]
-                d_sh = torch.empty((P, sh_M, 3), dtype=rz._F32, device=device) if has_sh and nd[2] else None
+                want = (nd[0], nd[1], has_col and nd[3], nd[4], has_sc and nd[5], has_rot and nd[6], has_cov and nd[7])
+                want_sh = has_sh and nd[2]
+                dgrads = rz._grad_arena(P, want, want_sh, sh_M, device)
+                d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov, d_sh = dgrads
                 grad_ws = rz._workspace(rz._sizes(P, W, H, jb.capacity).grad_bytes, device)      # (B's Gaussian-major instance numbering)
-                keep += [g_color, g_depth, g_alpha, grad_ws]
+                keep += [*image_grads, grad_ws]
                 a = arr[k]
-                a.settings = ctypes.pointer(c.settings)
-                a.P, a.sh_M = P, sh_M
-                b_m3, b_sh, b_col, b_op, b_sc, b_rot, b_cov = saved[7 * k: 7 * k + 7]
-                a.means3D = b_m3.data_ptr()
-                a.shs = b_sh.data_ptr() if has_sh else None
-                a.colors_precomp = b_col.data_ptr() if has_col else None
-                a.opacities = b_op.data_ptr()
-                a.scales = b_sc.data_ptr() if has_sc else None
-                a.rotations = b_rot.data_ptr() if has_rot else None
-                a.cov3D_precomp = b_cov.data_ptr() if has_cov else None
-                a.radii = jb.radii.data_ptr()
-                a.geom_ws, a.tile_ws, a.bin_ws, a.capacity = jb.geom_ptr, c.tile_ptr, c.bin_ptr, c.capacity
-                a.dL_dcolor, a.dL_ddepth, a.dL_dalpha = g_color.data_ptr(), rz._addr(g_depth), rz._addr(g_alpha)
-                if rz._capture_grad_ind is not None:
-                    a.dL_dcolor_indirect = rz._capture_grad_ind.get(g_color.data_ptr())
-                a.grad_ws = grad_ws.data_ptr()
-                a.dL_dmeans2D, a.dL_dmeans3D, a.dL_dcolors = rz._addr(d_means2D), rz._addr(d_means3D), rz._addr(d_colors)
-                a.dL_dopacity, a.dL_dscales, a.dL_drotations = rz._addr(d_opac), rz._addr(d_scales), rz._addr(d_rot)
-                a.dL_dsh, a.dL_dcov3D = rz._addr(d_sh), rz._addr(d_cov)
-                a.grad_first = 0
+                rz._fill_backward_job(a, c.settings, P, sh_M, inputs7, jb.radii, (jb.geom_ptr, c.tile_ptr, c.bin_ptr), c.capacity,
+                                      image_grads, grad_ws, dgrads)
                 a.compose_geom_a, a.compose_P_a, a.compose_capacity_b = ja.geom_ptr, ja.P, jb.capacity
                 # the composite's packed lists fill a fraction of its buffer (sized for both sources): its own report, written
                 # by the first kernel of its forward, says how many batch slots the backward has to visit
@@ -224,8 +192,7 @@ class _Compose(torch.autograd.Function):
                 if ctx.fold and (jb.stash is None or jb.stash[0] == me):
                     # leave them with B's job: B's own backward runs after this one (the token orders it) and adds its
                     # gradients to these buffers inside its per-Gaussian kernel, then returns them as the tensors' gradients
-                    jb.stash = (me, rz._grad_pattern(nd[0], d_sh is not None, has_col and nd[3], nd[4], has_sc and nd[5],
-                                                  has_rot and nd[6], has_cov and nd[7]),
+                    jb.stash = (me, (want[0], want_sh) + want[2:],          # (which of the seven below get a gradient)
                                 (d_means3D, d_sh, d_colors, d_opac, d_scales, d_rot, d_cov)) + ((side,) if side is not None else ())
                     n_stashed += 1
                     ret += [None, d_means2D, None, None, None, None, None, None]

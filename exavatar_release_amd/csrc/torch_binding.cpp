@@ -218,7 +218,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         if (!g_color.defined()) g_color = at::zeros({3, H, W}, f32);
         Tensor g_depth = grad_in(g_depth_in, 1, H, W), g_alpha = grad_in(g_alpha_in, 1, H, W);
         const bool has_dens = st->dens[0].defined() || st->dens[1].defined() || st->dens[2].defined();
-        // ONE arena for the small per-Gaussian gradients (layout of rasterizer._Rasterize.backward); dL/dsh stays its own tensor
+        // ONE arena for the small per-Gaussian gradients (the layout of rasterizer._grad_arena); dL/dsh stays its own tensor
         const bool want[7] = {needs(A_M3), needs(A_M2) || has_dens, needs(A_COL), needs(A_OP), needs(A_SC), needs(A_ROT), needs(A_COV)};
         static const int64_t width[7] = {3, 3, 3, 1, 3, 4, 6};
         int64_t total = 0;

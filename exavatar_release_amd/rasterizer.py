@@ -265,6 +265,17 @@ def _note(key, need):
         _seen_D[key] = need
 
 
+def _capacity_for(key, k=0):
+    """Instances a capacity-mode render of shape ``key`` (job ``k`` of its call) gets room for, before the caller rounds up
+    to whole 64-instance batch slots: ``config.fixed_capacity`` (one number, or one per job), else what earlier calls of
+    the shape needed x ``config.capacity_growth``, at least ``config.min_capacity``; 0 for a shape nobody measured yet."""
+    fc = config.fixed_capacity
+    if fc is not None:
+        return int(fc[k] if isinstance(fc, (list, tuple)) else fc)
+    seen = _seen_D.get(key)
+    return 0 if seen is None else max(int(seen * config.capacity_growth), config.min_capacity)
+
+
 def _overflow_error(need, cap):
     return RuntimeError('exavatar_release_amd: tile-instance buffer overflow (needed %d, capacity %d). '
                         'Use config.on_overflow="retry", config.mode="exact" or raise config.capacity_growth.' % (need, cap))
@@ -273,28 +284,25 @@ def _overflow_error(need, cap):
 def _rerender(j, need, store_ctx, device):
     """Run job ``j``'s forward again with room for ``need`` instances, into the same output tensors."""
     lib = _lib.load()
-    cap = (max(int(need), 64) + 63) // 64 * 64
-    j.capacity = cap
-    j.ws = _workspace(j.gb + j.tb + int(_sizes(j.P, j.W, j.H, cap).bin_bytes), device)
-    j.bins = None
-    j.geom_ptr = j.ws.data_ptr()
-    j.tile_ptr = j.geom_ptr + j.gb
-    j.bin_ptr = j.tile_ptr + j.tb
+    _carve(j, (max(int(need), 64) + 63) // 64 * 64, device)
     arr = (_lib.ExaRasterForwardJob * 1)()
     _fill_forward_job(arr[0], j)
     _lib.check(lib.exa_raster_forward_batch(arr, 1, int(store_ctx), _stream_ptr(device)))
+
+
+def _read_needs(jobs):
+    """``(needed instances, overflow flag)`` per job, read back from the headers of the jobs' tile workspaces: ONE D2H copy
+    of 16 bytes per job + a stream synchronisation, as upstream does for every render."""
+    rows = [j.ws[j.gb:j.gb + 16].view(torch.int32) for j in jobs]
+    hdr = (rows[0] if len(jobs) == 1 else torch.stack(rows)).cpu().view(len(jobs), 4)
+    return [(int(hdr[k, 0]), int(hdr[k, 1])) for k in range(len(jobs))]
 
 
 def _settle(jobs, reports, store_ctx, device, stream):
     """Read the header reports of a capacity-mode call that was just queued (``reports``: one ``(slot, tag)`` per job, or
     None without a pool: the headers are read back) and deal with overflowed jobs (``config.on_overflow``) before the
     call's outputs leave ``forward``.  Every report is consumed before anything is raised."""
-    if reports is None:
-        rows = [j.ws[j.gb:j.gb + 16].view(torch.int32) for j in jobs]
-        hdr = (rows[0] if len(jobs) == 1 else torch.stack(rows)).cpu().view(len(jobs), 4)
-        got = [(int(hdr[k, 0]), int(hdr[k, 1])) for k in range(len(jobs))]
-    else:
-        got = [_await_report(r[0], r[1], stream) for r in reports]
+    got = _read_needs(jobs) if reports is None else [_await_report(r[0], r[1], stream) for r in reports]
     err = None
     for j, (need, overflow) in zip(jobs, got):
         _note(j.key, need)
@@ -352,6 +360,29 @@ _F32 = torch.float32
 _PLANES = [3, 1, 1]         # colour | depth | alpha planes of one output arena
 
 
+def _plane_ptrs(planes, H, W):
+    """Addresses of the colour, depth and alpha planes of one ``[5, H, W]`` float32 output arena."""
+    base = planes.data_ptr()
+    return base, base + 12 * H * W, base + 16 * H * W
+
+
+def _plane_outputs(planes):
+    """The ``[3, H, W]`` colour, ``[1, H, W]`` depth and ``[1, H, W]`` alpha views of an output arena."""
+    return torch.split_with_sizes(planes, _PLANES)       # (Tensor.split is a Python wrapper: ~4 us)
+
+
+def _carve(j, capacity, device, bins=True):
+    """ONE arena per render -- splat records | tile workspace | bin workspace for ``capacity`` instances -- allocated and
+    named in job ``j``.  ``bins=False`` (exact mode, capacity 0): no bin section, the bin workspace follows the header
+    read-back.  (A capacity-mode render keeps its bin section whatever the capacity, a fixed capacity of 0 included.)"""
+    j.capacity = capacity
+    j.bins = None
+    j.ws = _workspace(j.gb + j.tb + (int(_sizes(j.P, j.W, j.H, capacity).bin_bytes) if bins else 0), device)
+    j.geom_ptr = j.ws.data_ptr()
+    j.tile_ptr = j.geom_ptr + j.gb
+    j.bin_ptr = j.tile_ptr + j.tb if bins else None
+
+
 def _fill_forward_job(a, j, report=None):
     a.settings = ctypes.pointer(j.settings)
     a.P, a.sh_M = j.P, j.sh_M
@@ -361,8 +392,7 @@ def _fill_forward_job(a, j, report=None):
     a.radii = j.radii.data_ptr()
     a.is_vis = j.is_vis.data_ptr()
     a.geom_ws, a.tile_ws, a.bin_ws, a.capacity = j.geom_ptr, j.tile_ptr, j.bin_ptr, j.capacity
-    base = j.planes.data_ptr()
-    a.out_color, a.out_depth, a.out_alpha = base, base + 12 * j.H * j.W, base + 16 * j.H * j.W
+    a.out_color, a.out_depth, a.out_alpha = _plane_ptrs(j.planes, j.H, j.W)
     a.keep_sorted_keys = 1 if j.keep_keys else 0
     if report is not None:           # (slot, tag) of a pool slot
         a.host_header, a.header_tag = _hdr_pool.dev_base + 16 * report[0], report[1]
@@ -380,12 +410,53 @@ def _grad_in(g, shape, device):
     return g if g.is_contiguous() else g.contiguous()
 
 
+def _image_grads(grads4, H, W, device):
+    """``(dL/dcolor, dL/ddepth, dL/dalpha)`` of the ``(color, radii, depth, alpha)`` output gradients of one render: the
+    kernels need a colour gradient (zeros for a missing one) and take a null pointer for a missing depth / alpha one."""
+    g_color = _grad_in(grads4[0], (3, H, W), device)
+    if g_color is None:
+        g_color = torch.zeros((3, H, W), dtype=_F32, device=device)
+    return g_color, _grad_in(grads4[2], (1, H, W), device), _grad_in(grads4[3], (1, H, W), device)
+
+
+_GRAD_WIDTHS = (3, 3, 3, 1, 3, 4, 6)
+
+
+def _grad_arena(rows, want, want_sh, sh_M, device):
+    """``[d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov, d_sh]`` of one job: ``[rows, 3 | 3 | 3 | 1 | 3 |
+    4 | 6]`` views, in that order and closed up, of ONE arena for the entries of ``want`` that are on (None for the others:
+    the kernels take a null pointer for "no gradient") instead of up to seven allocator calls; ``d_sh [rows, sh_M, 3]``
+    (up to 48 floats per row) stays a tensor of its own.  AccumulateGrad adopts a contiguous view as ``.grad`` like any
+    other tensor.  THE layout of the gradient arena: csrc/torch_binding.cpp mirrors it (``RasterizeFn::backward``)."""
+    widths = [w for on, w in zip(want, _GRAD_WIDTHS) if on]
+    pieces = iter(torch.split_with_sizes(torch.empty(rows * sum(widths), dtype=_F32, device=device), [rows * w for w in widths])) \
+        if widths else iter(())
+    views = [next(pieces).view(rows, w) if on else None for on, w in zip(want, _GRAD_WIDTHS)]
+    views.append(torch.empty((rows, sh_M, 3), dtype=_F32, device=device) if want_sh else None)
+    return views
+
+
+def _fill_backward_job(a, settings, P, sh_M, inputs7, radii, ws_ptrs, capacity, image_grads, grad_ws, dgrads8):
+    """Every field of an ``ExaRasterBackwardJob`` that a plain and a composite render share.  ``inputs7``: means3D, sh,
+    colors, opacities, scales, rotations, cov3D as the forward saved them (None = not given); ``ws_ptrs``: (geom, tile, bin)
+    addresses; ``dgrads8``: what :func:`_grad_arena` returned.  What is left zero is the caller's: ``grad_first``,
+    ``accumulate``, ``used_slots``, ``densify_*``, ``compose_*``."""
+    a.settings = ctypes.pointer(settings)      # built in forward; its tensors are kept alive by the job's keep list
+    a.P, a.sh_M = P, sh_M
+    a.means3D, a.shs, a.colors_precomp, a.opacities, a.scales, a.rotations, a.cov3D_precomp = [_addr(t) for t in inputs7]
+    a.radii = radii.data_ptr()
+    a.geom_ws, a.tile_ws, a.bin_ws = ws_ptrs
+    a.capacity = capacity
+    g_color, g_depth, g_alpha = image_grads
+    a.dL_dcolor, a.dL_ddepth, a.dL_dalpha = g_color.data_ptr(), _addr(g_depth), _addr(g_alpha)
+    if _capture_grad_ind is not None:
+        a.dL_dcolor_indirect = _capture_grad_ind.get(g_color.data_ptr())
+    a.grad_ws = grad_ws.data_ptr()
+    a.dL_dmeans3D, a.dL_dmeans2D, a.dL_dcolors, a.dL_dopacity, a.dL_dscales, a.dL_drotations, a.dL_dcov3D, a.dL_dsh = \
+        [_addr(t) for t in dgrads8]
+
+
 N_IN = 8      # tensor arguments per job: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D
-
-
-def _grad_pattern(*wanted):
-    """Which of (means3D, sh, colors, opacity, scales, rotations, cov3D) get a gradient, as a tuple of bools."""
-    return tuple(bool(w) for w in wanted)
 
 
 class _Rasterize(torch.autograd.Function):
@@ -482,23 +553,10 @@ class _Rasterize(torch.autograd.Function):
                 j.stash = j.token_ref = j.need = None
                 sz = _sizes(j.P, j.W, j.H, 0)
                 j.gb, j.tb = int(sz.geom_bytes), int(sz.tile_bytes)
-                j.bins = None
                 if mode == 'capacity':
-                    if config.fixed_capacity is not None:
-                        fc = config.fixed_capacity
-                        cap = int(fc[k] if isinstance(fc, (list, tuple)) else fc)
-                    else:
-                        cap = max(int(_seen_D[j.key] * config.capacity_growth), config.min_capacity)
-                    j.capacity = (cap + 63) // 64 * 64
-                    # ONE arena per render: splat records | tile workspace | bin workspace
-                    j.ws = _workspace(j.gb + j.tb + int(_sizes(j.P, j.W, j.H, j.capacity).bin_bytes), device)
-                    j.bin_ptr = j.ws.data_ptr() + j.gb + j.tb
+                    _carve(j, (_capacity_for(j.key, k) + 63) // 64 * 64, device)
                 else:
-                    j.capacity = 0
-                    j.ws = _workspace(j.gb + j.tb, device)
-                    j.bin_ptr = None
-                j.geom_ptr = j.ws.data_ptr()
-                j.tile_ptr = j.geom_ptr + j.gb
+                    _carve(j, 0, device, bins=False)
                 rep = reports[k] if reports is not None else None
                 if capturing and _capture_report is not None and k < len(_capture_report):
                     rep = _capture_report[k]          # a reserved slot, read by the owner of the graph after each replay
@@ -506,12 +564,10 @@ class _Rasterize(torch.autograd.Function):
 
             if mode == 'exact':
                 _lib.check(lib.exa_raster_forward_bin_batch(arr, K, stream))
-                rows = [j.ws[j.gb:j.gb + 16].view(torch.int32) for j in jobs]
-                hdr = (rows[0] if K == 1 else torch.stack(rows)).cpu().view(K, 4)        # D2H + sync, as upstream does
-                for k, j in enumerate(jobs):
-                    j.capacity = max(int(hdr[k, 0]), 64)          # header reports whole 64-instance batch slots
-                    j.need = int(hdr[k, 0])
-                    _note(j.key, int(hdr[k, 0]))
+                for k, (j, (need, _overflow)) in enumerate(zip(jobs, _read_needs(jobs))):
+                    j.capacity = max(need, 64)          # header reports whole 64-instance batch slots
+                    j.need = need
+                    _note(j.key, need)
                     j.bins = _workspace(_sizes(j.P, j.W, j.H, j.capacity).bin_bytes, device)
                     j.bin_ptr = j.bins.data_ptr()
                     arr[k].bin_ws, arr[k].capacity = j.bin_ptr, j.capacity
@@ -547,7 +603,7 @@ class _Rasterize(torch.autograd.Function):
         ctx.need_ctx = need_ctx
         outs = []
         for j in jobs:
-            c, d, a = torch.split_with_sizes(j.planes, _PLANES)       # (Tensor.split is a Python wrapper: ~4 us)
+            c, d, a = _plane_outputs(j.planes)
             outs += [c, j.radii, d, a]
         if keep_keys:
             # One more (empty) differentiable output: composites of these renders take it as an input, which orders their
@@ -560,17 +616,9 @@ class _Rasterize(torch.autograd.Function):
             ctx.densify = densify
             ctx.shared = bool(shared) and K > 1
             ctx.jobs = jobs
-            ctx.has = [tuple(t is not None for t in (j.sh, j.colors, j.scales, j.rot, j.cov)) for j in jobs]
             saved = []
-            empty = None
-            for j in jobs:
-                for t in (j.means3D, j.sh, j.colors, j.opac, j.scales, j.rot, j.cov):
-                    if t is None:
-                        if empty is None:
-                            empty = torch.empty(0, device=device)
-                        t = empty
-                    saved.append(t)
-                saved.append(j.radii)
+            for j in jobs:                  # (an input that was not given is saved, and handed back, as None)
+                saved += [j.means3D, j.sh, j.colors, j.opac, j.scales, j.rot, j.cov, j.radii]
             ctx.save_for_backward(*saved)
         ctx.mark_non_differentiable(*[outs[4 * k + 1] for k in range(K)])
         # outputs nobody differentiates (radii, and depth / alpha when the loss ignores them) reach backward as None
@@ -600,9 +648,8 @@ class _Rasterize(torch.autograd.Function):
                 j = ctx.jobs[k]
                 P, H, W, sh_M, nF = j.P, j.H, j.W, j.sh_M, j.nF
                 Pg = P - nF                               # rows of every gradient array (constant prefix excluded)
-                has_sh, has_col, has_sc, has_rot, has_cov = ctx.has[k]
-                means3D, sh, col, opac, scales, rot, cov, radii = saved[8 * k: 8 * k + 8]
-                g_color, g_depth, g_alpha = grads[4 * k], grads[4 * k + 2], grads[4 * k + 3]
+                inputs7, radii = saved[8 * k: 8 * k + 7], saved[8 * k + 7]
+                _, has_sh, has_col, _, has_sc, has_rot, has_cov = [t is not None for t in inputs7]
                 if dead[k]:
                     st, j.stash = j.stash, None
                     if st is not None and len(st) > 3:
@@ -614,63 +661,31 @@ class _Rasterize(torch.autograd.Function):
                         ret += [h3, None, hsh, hcol, hop, hsc, hrot, hcov]
                     continue
 
-                g_color = _grad_in(g_color, (3, H, W), device)
-                if g_color is None:
-                    g_color = torch.zeros((3, H, W), dtype=_F32, device=device)
-                if g_depth is not None:
-                    g_depth = _grad_in(g_depth, (1, H, W), device)
-                if g_alpha is not None:
-                    g_alpha = _grad_in(g_alpha, (1, H, W), device)
+                image_grads = _image_grads(grads[4 * k: 4 * k + 4], H, W, device)
                 nd = need[N_IN * k: N_IN * (k + 1)]
                 own = (not ctx.shared) or k == 0          # shared: job 0's outputs receive the sum over the K views
-                # ONE arena for the small per-Gaussian gradients of this job (3 + 3 + 3 + 1 + 3 + 4 + 6 floats per row at
-                # most) instead of up to seven allocator calls; dL/dsh (up to 48 floats per row) stays its own tensor.
-                # AccumulateGrad adopts a contiguous view as `.grad` like any other tensor.
-                want = ((own and nd[0], 3), (nd[1], 3), (own and has_col and nd[3], 3), (own and nd[4], 1),
-                        (own and has_sc and nd[5], 3), (own and has_rot and nd[6], 4), (own and has_cov and nd[7], 6))
+                want = (own and nd[0], nd[1], own and has_col and nd[3], own and nd[4], own and has_sc and nd[5],
+                        own and has_rot and nd[6], own and has_cov and nd[7])         # (in the order of _grad_arena)
                 want_sh = own and has_sh and nd[2]
                 # gradients a composite render left for these Gaussians (_Compose.backward): this call adds its own to them
                 st, j.stash = j.stash, None
                 if st is not None and len(st) > 3:
                     sides.add(st[3])              # (recorded on a side stream inside a capture: joined before it is read)
-                fold = st is not None and not ctx.shared and nF == 0 and \
-                    st[1] == _grad_pattern(want[0][0], want_sh, want[2][0], want[3][0], want[4][0], want[5][0], want[6][0])
+                fold = st is not None and not ctx.shared and nF == 0 and st[1] == (want[0], want_sh) + want[2:]
                 if fold:
                     d_means3D, d_sh, d_colors, d_opac, d_scales, d_rot, d_cov = st[2]
                     d_means2D = torch.empty((Pg, 3), dtype=_F32, device=device) if nd[1] else None
                 else:
-                    widths = [w for on, w in want if on]
-                    pieces = iter(torch.split_with_sizes(torch.empty(Pg * sum(widths), dtype=_F32, device=device), [Pg * w for w in widths])) \
-                        if widths else iter(())
-                    d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov = \
-                        [next(pieces).view(Pg, w) if on else None for on, w in want]
-                    d_sh = torch.empty((Pg, sh_M, 3), dtype=_F32, device=device) if want_sh else None
+                    d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov, d_sh = _grad_arena(Pg, want, want_sh, sh_M, device)
                     if st is not None:          # (a pattern this kernel path does not add in place: summed below)
                         late += [(d, h) for d, h in zip((d_means3D, d_sh, d_colors, d_opac, d_scales, d_rot, d_cov), st[2])
                                  if d is not None and h is not None]
                 grad_ws = _workspace(_sizes(P, W, H, j.capacity).grad_bytes, device)
-                keep += [g_color, g_depth, g_alpha, grad_ws]
+                keep += [*image_grads, grad_ws]
                 a = arr[pos]
                 pos += 1
-                a.settings = ctypes.pointer(j.settings)   # built in forward; its tensors are kept alive by j.keep
-                a.P, a.sh_M = P, sh_M
-                a.means3D = means3D.data_ptr()
-                a.shs = sh.data_ptr() if has_sh else None
-                a.colors_precomp = col.data_ptr() if has_col else None
-                a.opacities = opac.data_ptr()
-                a.scales = scales.data_ptr() if has_sc else None
-                a.rotations = rot.data_ptr() if has_rot else None
-                a.cov3D_precomp = cov.data_ptr() if has_cov else None
-                a.radii = radii.data_ptr()
-                a.geom_ws, a.tile_ws, a.bin_ws = j.geom_ptr, j.tile_ptr, j.bin_ptr
-                a.capacity = j.capacity
-                a.dL_dcolor, a.dL_ddepth, a.dL_dalpha = g_color.data_ptr(), _addr(g_depth), _addr(g_alpha)
-                if _capture_grad_ind is not None:
-                    a.dL_dcolor_indirect = _capture_grad_ind.get(g_color.data_ptr())
-                a.grad_ws = grad_ws.data_ptr()
-                a.dL_dmeans2D, a.dL_dmeans3D, a.dL_dcolors = _addr(d_means2D), _addr(d_means3D), _addr(d_colors)
-                a.dL_dopacity, a.dL_dscales, a.dL_drotations = _addr(d_opac), _addr(d_scales), _addr(d_rot)
-                a.dL_dsh, a.dL_dcov3D = _addr(d_sh), _addr(d_cov)
+                _fill_backward_job(a, j.settings, P, sh_M, inputs7, radii, (j.geom_ptr, j.tile_ptr, j.bin_ptr), j.capacity,
+                                   image_grads, grad_ws, (d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rot, d_cov, d_sh))
                 dens = ctx.densify[k] if ctx.densify is not None else None
                 if dens is not None:
                     if d_means2D is None:          # the statistics need the screen-space gradient: compute it anyway
@@ -779,14 +794,8 @@ def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales,
     if not node:
         return None
     key = (means3D.device.index, means3D.shape[0], rs[0], rs[1])
-    cap = 0                       # 'exact': two stages with a host round trip in between, as upstream does
-    if mode != 'exact':
-        cap = cfg.fixed_capacity
-        if cap is None:
-            seen = _seen_D.get(key)       # (first call of a shape: measured exactly once)
-            cap = 0 if seen is None else max(int(seen * cfg.capacity_growth), cfg.min_capacity)
-        elif isinstance(cap, (list, tuple)):
-            cap = cap[0]
+    # capacity 0 ('exact', or the first call of a shape): two stages with a host round trip in between, as upstream does
+    cap = _capacity_for(key) if mode != 'exact' else 0
     res = node.rasterize(rs, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, int(cap),
                          mode == 'auto', cfg.poison, dens)
     if res is None:
@@ -794,8 +803,7 @@ def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales,
     global compiled_calls
     compiled_calls += 1
     color, radii, depth, alpha, is_vis, need, overflowed = res
-    if need > _seen_D.get(key, 0):
-        _seen_D[key] = need
+    _note(key, need)
     if overflowed:
         _record_overflow(key, need, overflowed, 'retried')
     _tls.is_vis = [is_vis]

@@ -218,8 +218,7 @@ class StaticRender:
         a.settings = ctypes.pointer(s)
         a.keep_sorted_keys = 0
         a.host_header, a.header_tag = (sl.report[2], 0) if sl.report is not None else (None, 0)
-        base = sl.planes.data_ptr()
-        a.out_color, a.out_depth, a.out_alpha = base, base + 12 * self.H * self.W, base + 16 * self.H * self.W
+        a.out_color, a.out_depth, a.out_alpha = _rz._plane_ptrs(sl.planes, self.H, self.W)
         b = None
         if self.train:
             b = (_lib.ExaRasterBackwardJob * 1)()

@@ -1,0 +1,158 @@
+"""Host layer of the Gaussian rasterizer's autograd nodes (``rasterizer.py``): the pieces a plain and a composite render
+share -- gradient arena, backward job, output planes, capacity policy.  Plain CPU tensors (``data_ptr()`` works there), no
+library call."""
+import ctypes
+
+import pytest
+import torch
+
+from exavatar_release_amd import _lib
+from exavatar_release_amd import rasterizer as rz
+
+CPU = torch.device('cpu')
+WIDTHS = (3, 3, 3, 1, 3, 4, 6)
+
+
+def test_grad_arena_all_on_is_one_storage_in_the_documented_order():
+    rows = 37
+    *views, d_sh = rz._grad_arena(rows, (True,) * 7, False, 0, CPU)
+    assert d_sh is None and len(views) == 7
+    base = views[0].data_ptr()
+    for v, w, off in zip(views, WIDTHS, (0, 3, 6, 9, 10, 13, 17)):
+        assert v.shape == (rows, w) and v.dtype == torch.float32 and v.is_contiguous()
+        assert v.untyped_storage().data_ptr() == views[0].untyped_storage().data_ptr()
+        assert v.storage_offset() == rows * off and v.data_ptr() == base + 4 * rows * off
+    assert views[0].untyped_storage().nbytes() == 4 * rows * 23
+
+
+def test_grad_arena_partial_patterns_close_up_in_order():
+    rows = 5
+    want = (False, True, False, True, False, True, True)             # means2D, opacity, rotations, cov3D
+    *views, d_sh = rz._grad_arena(rows, want, False, 0, CPU)
+    assert [v is not None for v in views] == list(want) and d_sh is None
+    on = [v for v in views if v is not None]
+    assert [tuple(v.shape) for v in on] == [(rows, 3), (rows, 1), (rows, 4), (rows, 6)]
+    assert [v.storage_offset() for v in on] == [0, rows * 3, rows * 4, rows * 8]
+    assert len({v.untyped_storage().data_ptr() for v in on}) == 1 and on[0].untyped_storage().nbytes() == 4 * rows * 14
+    assert rz._grad_arena(rows, (False,) * 7, False, 0, CPU) == [None] * 8          # all off: nothing is allocated
+
+
+def test_grad_arena_d_sh_is_a_tensor_of_its_own():
+    rows, M = 6, 9
+    *views, d_sh = rz._grad_arena(rows, (True,) + (False,) * 6, True, M, CPU)
+    assert d_sh.shape == (rows, M, 3) and d_sh.dtype == torch.float32 and d_sh.is_contiguous()
+    assert d_sh.untyped_storage().data_ptr() != views[0].untyped_storage().data_ptr()
+    assert views[0].untyped_storage().nbytes() == 4 * rows * 3
+    only_sh = rz._grad_arena(rows, (False,) * 7, True, M, CPU)
+    assert only_sh[:7] == [None] * 7 and only_sh[7].shape == (rows, M, 3)
+
+
+def test_grad_arena_of_zero_rows():
+    *views, d_sh = rz._grad_arena(0, (True,) * 7, True, 4, CPU)
+    assert [tuple(v.shape) for v in views] == [(0, w) for w in WIDTHS] and d_sh.shape == (0, 4, 3)
+
+
+INPUT_FIELDS = ('means3D', 'shs', 'colors_precomp', 'opacities', 'scales', 'rotations', 'cov3D_precomp')
+GRAD_FIELDS = ('dL_dmeans3D', 'dL_dmeans2D', 'dL_dcolors', 'dL_dopacity', 'dL_dscales', 'dL_drotations', 'dL_dcov3D', 'dL_dsh')
+
+
+@pytest.mark.parametrize('with_cov', [True, False])
+def test_fill_backward_job_names_every_tensor_and_leaves_the_callers_fields_zero(with_cov):
+    P, M, H, W = 7, 4, 5, 9
+    t = lambda *shape: torch.zeros(shape)           # noqa: E731
+    if with_cov:        # colours + a precomputed covariance: no shs / scales / rotations
+        inputs7 = (t(P, 3), None, t(P, 3), t(P, 1), None, None, t(P, 6))
+        sh_M = 0
+    else:               # the reverse
+        inputs7 = (t(P, 3), t(P, M, 3), None, t(P, 1), t(P, 3), t(P, 4), None)
+        sh_M = M
+    want = tuple(x is not None for x in (inputs7[0], True, inputs7[2], inputs7[3], inputs7[4], inputs7[5], inputs7[6]))
+    dgrads8 = rz._grad_arena(P, want, inputs7[1] is not None, sh_M, CPU)
+    assert [d is not None for d in dgrads8[:7]] == list(want)
+    radii, grad_ws = torch.zeros(P, dtype=torch.int32), torch.zeros(64, dtype=torch.uint8)
+    image_grads = (t(3, H, W), None, t(1, H, W)) if with_cov else (t(3, H, W), t(1, H, W), None)
+    settings = _lib.ExaRasterSettings()
+    arr = (_lib.ExaRasterBackwardJob * 1)()
+    a = arr[0]
+    rz._fill_backward_job(a, settings, P, sh_M, inputs7, radii, (1024, 2048, 4096), 640, image_grads, grad_ws, dgrads8)
+    assert ctypes.addressof(a.settings.contents) == ctypes.addressof(settings)
+    assert (a.P, a.sh_M, a.capacity) == (P, sh_M, 640)
+    assert (a.geom_ws, a.tile_ws, a.bin_ws) == (1024, 2048, 4096)
+    for name, x in zip(INPUT_FIELDS + GRAD_FIELDS + ('dL_dcolor', 'dL_ddepth', 'dL_dalpha', 'radii', 'grad_ws'),
+                       tuple(inputs7) + tuple(dgrads8) + image_grads + (radii, grad_ws)):
+        assert getattr(a, name) == (None if x is None else x.data_ptr()), name          # (a NULL c_void_p reads as None)
+    assert a.dL_dcolor_indirect is None
+    # what the two callers own stays as the zero-initialised structure had it
+    assert (a.grad_first, a.accumulate, a.used_slots, a.compose_P_a, a.compose_capacity_b) == (0, 0, 0, 0, 0)
+    assert a.compose_geom_a is None
+    assert (a.densify_grad_accum, a.densify_track_cnt, a.densify_radius_max) == (None, None, None)
+
+
+def test_fill_backward_job_looks_up_the_indirect_colour_gradient_while_a_backward_is_recorded(monkeypatch):
+    """``dL_dcolor_indirect``: the pointer-table entry a recorded backward reads dL/dcolor through, found by the address of the
+    colour gradient in ``_capture_grad_ind``; a gradient the table does not name gets none."""
+    P, H, W = 3, 4, 6
+    inputs7 = (torch.zeros(P, 3), None, torch.zeros(P, 3), torch.zeros(P, 1), torch.zeros(P, 3), torch.zeros(P, 4), None)
+    radii, grad_ws = torch.zeros(P, dtype=torch.int32), torch.zeros(64, dtype=torch.uint8)
+    known, other = torch.zeros(3, H, W), torch.zeros(3, H, W)
+    monkeypatch.setattr(rz, '_capture_grad_ind', {known.data_ptr(): 0x7000})
+    for g_color, expect in ((known, 0x7000), (other, None)):
+        arr = (_lib.ExaRasterBackwardJob * 1)()
+        rz._fill_backward_job(arr[0], _lib.ExaRasterSettings(), P, 0, inputs7, radii, (64, 128, 192), 64, (g_color, None, None),
+                              grad_ws, [None] * 8)
+        assert arr[0].dL_dcolor == g_color.data_ptr() and arr[0].dL_dcolor_indirect == expect
+
+
+def test_image_grads_fill_in_a_missing_colour_and_keep_missing_planes_none():
+    H, W = 5, 9
+    g = torch.ones(3, H, W)
+    color, depth, alpha = rz._image_grads((g, None, None, None), H, W, CPU)
+    assert color is g and depth is None and alpha is None
+    color, depth, alpha = rz._image_grads((None, None, torch.ones(1, H, W, dtype=torch.float64), None), H, W, CPU)
+    assert color.shape == (3, H, W) and not color.any() and alpha is None
+    assert depth.dtype == torch.float32 and depth.shape == (1, H, W) and depth.is_contiguous()
+
+
+def test_plane_ptrs_and_outputs_of_a_ragged_image():
+    H, W = 37, 53
+    planes = torch.zeros(5, H, W)
+    base = planes.data_ptr()
+    assert rz._plane_ptrs(planes, H, W) == (base, base + 12 * H * W, base + 16 * H * W)
+    color, depth, alpha = rz._plane_outputs(planes)
+    assert (color.shape, depth.shape, alpha.shape) == ((3, H, W), (1, H, W), (1, H, W))
+    assert (color.data_ptr(), depth.data_ptr(), alpha.data_ptr()) == rz._plane_ptrs(planes, H, W)
+
+
+@pytest.fixture
+def policy():
+    """A temporary capacity policy: ``config`` and the capacity memo are put back afterwards."""
+    cfg = rz.config
+    saved = (cfg.fixed_capacity, cfg.capacity_growth, cfg.min_capacity)
+    key = ('test_raster_host', 1, 2, 3)
+    yield cfg, key
+    cfg.fixed_capacity, cfg.capacity_growth, cfg.min_capacity = saved
+    rz._seen_D.pop(key, None)
+
+
+def test_capacity_for_states_the_policy_once(policy):
+    cfg, key = policy
+    cfg.capacity_growth, cfg.min_capacity = 1.5, 1000
+    # a fixed capacity wins over what was seen: one number for every job, or one per job -- not rounded here: the Python
+    # node rounds up to whole 64-instance batch slots when it carves the workspace, the compiled node rounds in C++
+    rz._seen_D[key] = 5000
+    cfg.fixed_capacity = 1001
+    assert rz._capacity_for(key, 0) == rz._capacity_for(key, 3) == rz._capacity_for(key) == 1001
+    cfg.fixed_capacity = [130, 70000.0, 64]
+    assert [rz._capacity_for(key, k) for k in range(3)] == [130, 70000, 64] and rz._capacity_for(key) == 130
+    assert all(type(rz._capacity_for(key, k)) is int for k in range(3))
+    # no fixed capacity: what was seen x growth, at least min_capacity
+    cfg.fixed_capacity = None
+    rz._seen_D[key] = 600                        # 600 x 1.5 = 900 < min_capacity
+    assert rz._capacity_for(key, 0) == 1000
+    rz._seen_D[key] = 667                        # 1000.5: truncated, equal to the floor
+    assert rz._capacity_for(key, 0) == 1000
+    rz._seen_D[key] = 4001                       # 6001.5: truncated, NOT a multiple of 64
+    assert rz._capacity_for(key, 1) == 6001
+    # a shape nobody measured: 0 = measure it (exact mode)
+    del rz._seen_D[key]
+    assert rz._capacity_for(key, 0) == 0
