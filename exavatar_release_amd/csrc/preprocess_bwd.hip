@@ -45,10 +45,24 @@ namespace exa {
 // sums ITS instances from LDS in slot order -- the very order and arithmetic of the old per-lane loop (an unflagged slot adds
 // +0), so the results are bit-identical to it.  Two dependent global round trips per GCH slots of the whole wave instead of
 // per eight instances of its slowest lane.  Splats with >= COOP_MIN instances keep their own whole-wave path.
+// The chain of dependent trips IS the kernel's time (one wave lifetime: every wave of C3 is resident at once, and every one
+// of them has a stream of 330-455 slots = two chunks), and only row 3 of the splat records decides the slot of every stream
+// position.  So the first GCAP positions -- every wave of C3 -- take THREE trips instead of 1 + 2 per chunk: row 3; the
+// `touched` bytes of all their chunks in one request; the flagged records of all their chunks, chunk c + 1's in flight (in
+// registers of their own: the chunk loop is unrolled) while chunk c is staged and summed.  The slot searches of a chunk run
+// side by side (branch-free; they were seven dependent LDS reads each, one search after the other).  A stream longer than
+// GCAP continues with the two trips per chunk, and so does a record array of 4 GiB and more (pointer loads).  The order of
+// every lane's additions is untouched.  GCAP = 512: 140 VGPRs in the plain kernel (three waves per SIMD up to 168), 1 024
+// takes 174.  (C3, phases per wave on the 100 MHz clock, tools/gpu_pbwd_phases.py: profiles/pbwd_gather_ab.md.)
 #ifndef EXA_PBWD_GCH
 #define EXA_PBWD_GCH 256
 #endif
 constexpr int GCH = EXA_PBWD_GCH;             // staged slots per chunk and wave (48 B of LDS each)
+#ifndef EXA_PBWD_GCAP
+#define EXA_PBWD_GCAP 512
+#endif
+constexpr int GCAP = EXA_PBWD_GCAP;           // stream positions whose `touched` bytes are requested in one trip
+static_assert(GCH % 64 == 0 && GCAP % GCH == 0 && GCAP / 64 <= 32, "whole chunks under the cap, one flag bit per position");
 struct GatherLds {
     uint32_t pre[64], off[64];
     float4 rec[GCH * 3];
@@ -75,7 +89,86 @@ __device__ __forceinline__ void stream_gather(uint32_t off, uint32_t n, const ui
     if (S == 0u) return;
     L.pre[lane] = pre; L.off[lane] = off;
     wave_lds_fence();
-    for (uint32_t c0 = 0; c0 < S; c0 += GCH) {
+    // the LAST lane g with pre[g] <= q owns stream position q (lanes without instances share their successor's prefix).
+    // A position past the end takes the stream's last slot -- any address that is valid to read -- by clamping q, NOT by a
+    // select on the result: behind a select the compiler sinks every search into a branch region of its own, and the
+    // searches of a chunk, seven dependent LDS reads each, run one after the other instead of side by side.
+    auto slot_of = [&](uint32_t q) -> uint32_t {
+        q = q < S ? q : S - 1u;
+        uint32_t g = 0;
+#pragma unroll
+        for (int s2 = 32; s2 > 0; s2 >>= 1)
+            if (L.pre[g + s2] <= q) g += s2;
+        return L.off[g] + (q - L.pre[g]);
+    };
+    // each lane adds ITS instances of the chunk staged at c0, in slot order
+    auto sum_chunk = [&](uint32_t c0) {
+        const uint32_t lo = pre > c0 ? pre : c0, hi = (pre + n) < (c0 + GCH) ? (pre + n) : (c0 + GCH);
+        for (uint32_t j = lo; j < hi; ++j) {
+            const float4* src = L.rec + (j - c0) * 3;
+            const float4 q0 = src[0], q1 = src[1], q2 = src[2];
+            sum[0] += q0.x; sum[1] += q0.y; sum[2] += q0.z; sum[3] += q0.w;
+            sum[4] += q1.x; sum[5] += q1.y; sum[6] += q1.z; sum[7] += q1.w;
+            sum[8] += q2.x; sum[9] += q2.y;
+        }
+    };
+    uint32_t c0 = 0;
+    if (use_buf) {
+        // ---- the first GCAP stream positions: ONE trip for all their `touched` bytes, then the chunks' records pipelined ----
+        // (Fully unrolled: every slot / flag / record register is named at compile time, and a chunk's loads and their
+        //  first use sit in different straight-line blocks.  The guards are wave-uniform.)
+        constexpr int NC = GCAP / GCH, PC = GCH / 64;                   // chunks under the cap, positions per lane and chunk
+        uint32_t slot[NC * PC], tch[NC * PC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+#pragma unroll
+            for (int u = 0; u < PC; ++u) { slot[c * PC + u] = off; tch[c * PC + u] = 0u; }
+            if ((uint32_t)(c * GCH) < S) {
+#pragma unroll
+                for (int u = 0; u < PC; ++u) slot[c * PC + u] = slot_of((uint32_t)(c * GCH + 64 * u) + (uint32_t)lane);
+#pragma unroll
+                for (int u = 0; u < PC; ++u) tch[c * PC + u] = touched[slot[c * PC + u]];   // all requests leave back to back
+            }
+        }
+        uint32_t fl = 0;                                                // bit i: position i of this lane is flagged
+#pragma unroll
+        for (int i = 0; i < NC * PC; ++i)
+            fl |= ((uint32_t)((i / PC) * GCH + 64 * (i % PC)) + (uint32_t)lane < S && tch[i]) ? (1u << i) : 0u;
+        // the records of chunk c: twelve buffer loads back to back; an unflagged position (or one past the stream, or a
+        // chunk past it) is pushed out of range and costs no memory request
+        float4 r0[NC][PC], r1[NC][PC], r2[NC][PC];
+        auto fetch = [&](int c) {
+#pragma unroll
+            for (int u = 0; u < PC; ++u) {
+                const uint32_t bo = ((fl >> (c * PC + u)) & 1u) ? slot[c * PC + u] * (uint32_t)PARTIAL_BYTES : BUF_OOB;
+                r0[c][u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, bo, 0, 0));
+                r1[c][u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, bo + 16u, 0, 0));
+                if (PARTIAL_BYTES == 40) {
+                    const float2 t = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, bo + 32u, 0, 0));
+                    r2[c][u] = make_float4(t.x, t.y, 0.f, 0.f);
+                } else {
+                    r2[c][u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, bo + 32u, 0, 0));
+                }
+            }
+        };
+        fetch(0);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if ((uint32_t)(c * GCH) >= S) break;
+            if (c + 1 < NC) fetch(c + 1);                               // in flight while chunk c is staged and summed
+#pragma unroll
+            for (int u = 0; u < PC; ++u) {
+                float4* dst = L.rec + (64 * u + lane) * 3;
+                dst[0] = r0[c][u]; dst[1] = r1[c][u]; dst[2] = r2[c][u];
+            }
+            wave_lds_fence();
+            sum_chunk((uint32_t)(c * GCH));
+            wave_lds_fence();                                           // the next chunk overwrites the staging area
+            c0 = (uint32_t)((c + 1) * GCH);
+        }
+    }
+    // ---- the rest of a stream longer than GCAP (and the pointer path): two dependent trips per chunk ----
+    for (; c0 < S; c0 += GCH) {
         // (Every loop below is its own straight-line block ON PURPOSE: with a load and its first use -- or a conditional
         //  load and the store of its result -- in one loop body the compiler emits one branch region per iteration and an
         //  `s_waitcnt vmcnt(0)` at each join: eight serial round trips per chunk instead of two.)
@@ -85,12 +178,7 @@ __device__ __forceinline__ void stream_gather(uint32_t off, uint32_t n, const ui
         for (int u = 0; u < GCH / 64; ++u) {
             const uint32_t q = c0 + 64u * u + (uint32_t)lane;
             in[u] = q < S;
-            // the LAST lane g with pre[g] <= q owns position q (lanes without instances share their successor's prefix)
-            uint32_t g = 0;
-#pragma unroll
-            for (int s2 = 32; s2 > 0; s2 >>= 1)
-                if (L.pre[g + s2] <= q) g += s2;
-            slot[u] = in[u] ? L.off[g] + (q - L.pre[g]) : off;          // (past the end: any address that is valid to read)
+            slot[u] = slot_of(q);
         }
 #pragma unroll
         for (int u = 0; u < GCH / 64; ++u) tch[u] = touched[slot[u]];   // unconditional: all requests leave back to back
@@ -127,14 +215,7 @@ __device__ __forceinline__ void stream_gather(uint32_t off, uint32_t n, const ui
             dst[0] = q0[u]; dst[1] = q1[u]; dst[2] = q2[u];
         }
         wave_lds_fence();
-        const uint32_t lo = pre > c0 ? pre : c0, hi = (pre + n) < (c0 + GCH) ? (pre + n) : (c0 + GCH);
-        for (uint32_t j = lo; j < hi; ++j) {
-            const float4* src = L.rec + (j - c0) * 3;
-            const float4 q0 = src[0], q1 = src[1], q2 = src[2];
-            sum[0] += q0.x; sum[1] += q0.y; sum[2] += q0.z; sum[3] += q0.w;
-            sum[4] += q1.x; sum[5] += q1.y; sum[6] += q1.z; sum[7] += q1.w;
-            sum[8] += q2.x; sum[9] += q2.y;
-        }
+        sum_chunk(c0);
         wave_lds_fence();                                           // the next chunk overwrites the staging area
     }
 }
@@ -220,17 +301,11 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
     const bool valid = idx < out.P && idx >= gf;
     const int idc = idx < out.P ? idx : out.P - 1;              // clamped index for loads
     const int row = idx - gf;                                   // output row
+    // (the inputs are loaded in the first trip of the view loop, BEHIND the loads that gate the gather)
     float in_s[3] = {0.f, 0.f, 0.f};
     float4 in_q = make_float4(1.f, 0.f, 0.f, 0.f);
     float in_cov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (out.cov3D_precomp) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) in_cov[i] = out.cov3D_precomp[idc * 6 + i];
-    } else {
-        in_s[0] = out.scales[idc * 3 + 0]; in_s[1] = out.scales[idc * 3 + 1]; in_s[2] = out.scales[idc * 3 + 2];
-        in_q = reinterpret_cast<const float4*>(out.rotations)[idc];
-    }
-    const float x = out.means3D[idc * 3 + 0], y = out.means3D[idc * 3 + 1], z = out.means3D[idc * 3 + 2];
+    float x = 0.f, y = 0.f, z = 0.f;
 
     float dmean[3] = {0.f, 0.f, 0.f}, dscale[3] = {0.f, 0.f, 0.f};
     float dq[4] = {0.f, 0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -248,11 +323,14 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
         const PreprocessBwdArgs& a = batch.v[SUM ? view : blockIdx.y];
         const float* __restrict__ v = a.viewmatrix;
         const float* __restrict__ p = a.projmatrix;
-        // r3 first: the partial gather depends on it
+        // What gates the gather goes first and leaves together: row 3 of the splat record, the radius, the overflow word
+        // (all three unconditional: behind `valid && ...` the radius was requested only after the overflow word had arrived)
         const uint4 r3 = reinterpret_cast<const uint4*>(a.splats + idc)[3];
+        const int rad = a.radii[idc];
+        const uint32_t ovf = a.header->overflow;
         // an overflowed forward left no lists behind: every gradient of that view is zero (the overflow itself is
         // reported to the host through the header, include/exa_raster.h)
-        const bool vis = valid && a.header->overflow == 0u && a.radii[idc] > 0;
+        const bool vis = valid && ovf == 0u && rad > 0;
         const uint8_t* __restrict__ touched = a.touched;
         const float4* __restrict__ prec = a.partials.rec;
 
@@ -290,6 +368,20 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
         }
 
         PBWD_PHASE(0);                                          // splat row 3 here (first trip), heavy splats gathered
+        // The inputs, which only the chain rule reads: requested once, HERE -- behind the wait for row 3, in front of the
+        // gather's first request -- so that they are in flight during the gather and nothing waits for them before it.
+        // (In front of the view loop, as until round 6, the compiler waited for them BEFORE it requested row 3: it hoists
+        //  the quaternion products as far up as the loads allow.  Two serial round trips to the start of the gather.)
+        if (trip == 0) {
+            if (out.cov3D_precomp) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) in_cov[i] = out.cov3D_precomp[idc * 6 + i];
+            } else {
+                in_s[0] = out.scales[idc * 3 + 0]; in_s[1] = out.scales[idc * 3 + 1]; in_s[2] = out.scales[idc * 3 + 2];
+                in_q = reinterpret_cast<const float4*>(out.rotations)[idc];
+            }
+            x = out.means3D[idc * 3 + 0]; y = out.means3D[idc * 3 + 1]; z = out.means3D[idc * 3 + 2];
+        }
         // ---- this wave's blended instances (contiguous slots, each written at most once), gathered together ----------
         float own[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         stream_gather(r3.w, (vis && r3.z < COOP_MIN) ? r3.z : 0u, touched, prec, a.partial_bytes, own, s_gather[threadIdx.x >> 6], lane);
@@ -301,6 +393,18 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
             // contracts each on its own, and a view's gradients have to come out of the batched (SUM) instantiations as they
             // come out of the single-view ones (dL/dmean2D bit for bit: tests/test_gpu_parity.py, batched views)
 #pragma clang fp contract(off)
+            // (the inputs pass through an empty asm that stays behind the gather's fences: no arithmetic on them, and so no
+            //  wait for them, can move in front of the gather.  This holds because wave_lds_fence is a volatile asm and the
+            //  compiler keeps volatile asms in order; if it ever stops holding, the results stay right and only the
+            //  overlap, 1.7 us on C3, is lost.  The check is the ISA (hipcc -S): the s_waitcnt vmcnt that covers the loads of
+            //  scales / rotations / means3D must sit BEHIND the gather, not in front of its first request: look there after a
+            //  compiler upgrade)
+            if (out.cov3D_precomp) {
+                asm volatile("" : "+v"(in_cov[0]), "+v"(in_cov[1]), "+v"(in_cov[2]), "+v"(in_cov[3]), "+v"(in_cov[4]), "+v"(in_cov[5]));
+            } else {
+                asm volatile("" : "+v"(in_s[0]), "+v"(in_s[1]), "+v"(in_s[2]), "+v"(in_q.x), "+v"(in_q.y), "+v"(in_q.z), "+v"(in_q.w));
+            }
+            asm volatile("" : "+v"(x), "+v"(y), "+v"(z));
             float mx = own[0], my = own[1], mxx = own[2], mxy = own[3], myy = own[4], dz_view = own[9];
             vop = own[5]; vcol[0] = own[6]; vcol[1] = own[7]; vcol[2] = own[8];
 
@@ -507,11 +611,11 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
             if (SUM && dens_shared) {
                 dn_acc += grad_norm2(vm2[0], vm2[1]);
                 dn_cnt += 1.0f;
-                dn_rmax = fmaxf(dn_rmax, (float)a.radii[idc]);
+                dn_rmax = fmaxf(dn_rmax, (float)rad);
             } else {
                 if (a.dens_accum) a.dens_accum[row] += grad_norm2(vm2[0], vm2[1]);
                 if (a.dens_cnt) a.dens_cnt[row] += 1.0f;
-                if (a.dens_rmax) a.dens_rmax[row] = fmaxf(a.dens_rmax[row], (float)a.radii[idc]);
+                if (a.dens_rmax) a.dens_rmax[row] = fmaxf(a.dens_rmax[row], (float)rad);
             }
         }
 #pragma unroll
