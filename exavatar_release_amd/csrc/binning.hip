@@ -127,7 +127,8 @@ __device__ __forceinline__ unsigned long long block_excl_scan64(unsigned long lo
 // so the heaviest cells start early and the tail of the launch is light; the empty cells come last and
 // header.active_cells counts the others.  One workgroup; `inst_of(c)` returns the instance count of cell c.  Every
 // record carries the cell's entry range and first instance slot (cell_off, already written to global memory by this
-// workgroup), so that the per-cell workgroups of the next kernels need ONE load instead of a chain of three.
+// workgroup), so that the per-cell workgroups of the next kernels need ONE descriptor load instead of a chain of three (the
+// second trip of their prologue, common.h; the compiler makes one trip of it only when it is asked to, EXA_TOGETHER).
 // ADAPTIVE split of the cells over the BIN_PARTS * cells workgroups of the two-launch sub-tile binning (subtile_count /
 // subtile_bin below): a cell gets one workgroup per `per` entries (per >= 1024: one trip of their entry loop), at most
 // MAX_PARTS, at least one (an empty cell's workgroup publishes its empty ranges); the workgroups beyond the sum find
@@ -305,13 +306,21 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
     __shared__ unsigned long long s_tmp64[SC_BLOCK / 64];
     __shared__ uint32_t s_bcast[2];
     const BinArgs& a = batch.v[blockIdx.y];
-    const int P = a.P;
+    const TileWs& w = a.tw;                                      // (the publisher's and the unmerged path's fields: read where used)
+    // trip one: every field of the job record a scattering workgroup of the merged path uses (common.h: prologue discipline),
+    // and the launch width with them -- gridDim.x lives in the hidden arguments, a line far behind the job records, and
+    // was a scalar trip of its own in front of the zero-fill
+    int chunks = a.chunks;
+    const int P = a.P, merged = a.merged, cells = a.grid.cells, gcx = a.grid.cx;
     Splat* __restrict__ splats = a.splats;
-    const TileWs& w = a.tw;
-    const Grid& g = a.grid;
-    const BinWs& b = a.bw;
+    unsigned long long* chunk_cell = a.tw.chunk_cell;
+    const uint32_t* chunk_inst = a.tw.chunk_inst;
+    uint4* bucket = a.bw.bucket;
+    uint4* owner = a.bw.owner;
     const uint64_t capacity = a.capacity;
-    const int tid = threadIdx.x, cells = g.cells;
+    const uint32_t gdx = gridDim.x;
+    EXA_TOGETHER(chunks, P, merged, cells, gcx, splats, chunk_cell, chunk_inst, bucket, owner, capacity, gdx);
+    const int tid = threadIdx.x;
 #ifdef EXA_PROBE_SCATTER   // probe build only (tools/gpu_scatter_phases.py): phases of every workgroup on the 100 MHz clock
     const unsigned long long ps_t0 = wall_clock64();
 #define SCATTER_PHASE(i) do { __syncthreads(); if (tid == 0) w.part_cnt[40000 + 8 * blockIdx.x + (i)] = (uint32_t)(wall_clock64() - ps_t0); } while (0)
@@ -321,18 +330,18 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
 #endif
     {   // this workgroup's slice of the zero-filled section of the bin workspace: batch owners (written by
         // subtile_bin_kernel, the next launch), blended masks (render_fwd), touched bytes (render_bwd)
-        const size_t n16 = bin_zero_bytes(capacity) / 16, per = (n16 + gridDim.x - 1) / gridDim.x;
+        const size_t n16 = bin_zero_bytes(capacity) / 16, per = (n16 + gdx - 1) / gdx;
         const size_t lo = (size_t)blockIdx.x * per, hi = lo + per < n16 ? lo + per : n16;
-        for (size_t i = lo + threadIdx.x; i < hi; i += SC_BLOCK) b.owner[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (size_t i = lo + threadIdx.x; i < hi; i += SC_BLOCK) owner[i] = make_uint4(0u, 0u, 0u, 0u);
     }
     SCATTER_PHASE(0);                                            // zero-fill slice issued
     uint32_t* s_base = s_dyn;
     uint32_t* s_cnt2 = s_dyn + cells;
     // Merged scans: the workgroup AFTER the job's last chunk has no Gaussians to scatter; it is the one that publishes what
     // the later kernels read (cell_off, header, cell order), off the critical path of the scattering workgroups.
-    const bool publisher = a.merged && (int)blockIdx.x == a.chunks;
-    if ((int)blockIdx.x >= a.chunks && !publisher) {            // a job with fewer Gaussians than the largest of the batch
-        if (!a.merged && a.chunks == 0 && blockIdx.x == 0 && tid == 0 && a.host_hdr)
+    const bool publisher = merged && (int)blockIdx.x == chunks;
+    if ((int)blockIdx.x >= chunks && !publisher) {            // a job with fewer Gaussians than the largest of the batch
+        if (!merged && chunks == 0 && blockIdx.x == 0 && tid == 0 && a.host_hdr)
             report_header(a.host_hdr, w.header->num_rendered, 0u, 0u, a.hdr_tag);     // (cell_scan wrote the header)
         return;
     }
@@ -357,7 +366,7 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
         }
     };
     uint32_t D, chunk_off;
-    if (a.merged) {
+    if (merged) {
         // The scans of the (chunk, cell) count matrix, done redundantly by EVERY scatter workgroup instead of by two
         // tiny launches in front of it (col_scan + cell_scan: ~12 us of pure launch and memory latency for C3): column
         // totals, this chunk's entry offset in every cell, the prefix over the cells, the prefix of the chunks'
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
         unsigned long long* s_tot = reinterpret_cast<unsigned long long*>(s_dyn + 2 * cells);
         unsigned long long* s_bef = s_tot + cells;
         // (requested before the column walk: between the two block scans this load was a dependent trip of ~1 us)
-        const uint32_t ci = tid < a.chunks ? w.chunk_inst[tid] : 0u;
+        const uint32_t ci = tid < chunks ? chunk_inst[tid] : 0u;
         for (int c = tid; c < cells; c += SC_BLOCK) { s_tot[c] = 0ull; s_bef[c] = 0ull; }
         __syncthreads();
         {
@@ -376,9 +385,9 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
                 const int c2 = tid % cp, q = tid / cp;
                 if (q < G2) {
                     unsigned long long tot0 = 0ull, tot1 = 0ull, bef0 = 0ull, bef1 = 0ull;
-                    const ulonglong2* m = reinterpret_cast<const ulonglong2*>(w.chunk_cell) + c2;
+                    const ulonglong2* m = reinterpret_cast<const ulonglong2*>(chunk_cell) + c2;
 #pragma unroll 4
-                    for (int r = q; r < a.chunks; r += G2) {
+                    for (int r = q; r < chunks; r += G2) {
                         const ulonglong2 v = m[(size_t)r * cp];
                         const unsigned long long lowmask = r < (int)blockIdx.x ? 0xffffffffull : 0ull;
                         tot0 += v.x; tot1 += v.y;
@@ -394,9 +403,9 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
             const int c = tid % cells, q = tid / cells;
             if (q < G) {
                 unsigned long long tot = 0ull, bef = 0ull;
-                const unsigned long long* m = w.chunk_cell + c;
+                const unsigned long long* m = chunk_cell + c;
 #pragma unroll 4
-                for (int r = q; r < a.chunks; r += G) {
+                for (int r = q; r < chunks; r += G) {
                     const unsigned long long v = m[(size_t)r * cells];
                     tot += v;
                     bef += r < (int)blockIdx.x ? (v & 0xffffffffull) : 0ull;
@@ -422,7 +431,7 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
         if (publisher) {
             if (tid < cells) w.cell_off[tid] = make_uint2((uint32_t)x, (uint32_t)(x >> 32));
             unsigned long long vt;                               // tiles << 32 | visible (both sums stay < 2^32)
-            block_excl_scan64(tid < a.chunks ? ((unsigned long long)w.chunk_tiles[tid] << 32) | w.chunk_vis[tid] : 0ull, s_tmp64, vt);
+            block_excl_scan64(tid < chunks ? ((unsigned long long)w.chunk_tiles[tid] << 32) | w.chunk_vis[tid] : 0ull, s_tmp64, vt);
             const uint32_t vis_total = (uint32_t)vt;
             if (tid == 0) {
                 w.cell_off[cells] = make_uint2((uint32_t)tot_all, (uint32_t)(tot_all >> 32));
@@ -458,7 +467,7 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
         chunk_off = w.chunk_off[blockIdx.x];
         for (int c = tid; c < cells; c += SC_BLOCK) {
             s_cnt2[c] = 0u;
-            s_base[c] = w.cell_off[c].x + (uint32_t)w.chunk_cell[(size_t)blockIdx.x * cells + c];
+            s_base[c] = w.cell_off[c].x + (uint32_t)chunk_cell[(size_t)blockIdx.x * cells + c];
         }
     }
     __syncthreads();
@@ -476,10 +485,10 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
             const int sx0 = r3[it].x & 0xffff, sx1 = r3[it].x >> 16, sy0 = r3[it].y & 0xffff, sy1 = r3[it].y >> 16;
             for (int cy = sy0 >> 3; cy <= (sy1 - 1) >> 3; ++cy)
                 for (int cx = sx0 >> 3; cx <= (sx1 - 1) >> 3; ++cx) {
-                    const int c = cy * g.cx + cx;
+                    const int c = cy * gcx + cx;
                     const uint32_t r = __hip_atomic_fetch_add(&s_cnt2[c], 1u, __ATOMIC_RELAXED,
                                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                    b.bucket[s_base[c] + r] = make_uint4((uint32_t)ids[it], depth_bits[it], r3[it].x, r3[it].y);
+                    bucket[s_base[c] + r] = make_uint4((uint32_t)ids[it], depth_bits[it], r3[it].x, r3[it].y);
                 }
         }
     }
@@ -509,10 +518,11 @@ constexpr int BIN_THREADS = 1024;
 //  version spreads the same work over the chip.  Keeping several entries in flight per thread changes nothing in any of
 //  these loops either: they are not load-latency bound.)
 struct CellPart { int cell, part; uint32_t e0, e1, lo, hi, slot0; bool overflow, active; int rank, nparts; };
-// the work record of this workgroup from the table write_part_table left (ONE load, next to the header's); false: no work
-__device__ __forceinline__ bool cell_part_of(const TileWs& w, uint64_t capacity, CellPart& c) {
-    const uint4 d = w.part_desc[blockIdx.x];
-    const uint32_t need = w.header->num_rendered;
+// the work record of this workgroup from the table write_part_table left.  `d` = part_desc[blockIdx.x] and `need` =
+// header->num_rendered are loaded by the CALLER, together, in trip two of its prologue (common.h: EXA_TOGETHER): read through
+// the pointers here, the record came in two serial scalar trips (x, a branch, then y z w) with the header word in a third.
+// false: no work
+__device__ __forceinline__ bool cell_part_of(const uint4& d, uint32_t need, uint64_t capacity, CellPart& c) {
     if (d.x == NO_PART) return false;
     c.cell = (int)(d.x & 0xfffu); c.rank = (int)((d.x >> 12) & 0xfffu);
     c.part = (int)((d.x >> 24) & 0xfu); c.nparts = (int)(d.x >> 28) + 1;
@@ -523,12 +533,11 @@ __device__ __forceinline__ bool cell_part_of(const TileWs& w, uint64_t capacity,
     c.active = d.z > d.y || c.nparts > 1 || c.part > 0;          // a cell without entries has ONE part with an empty share
     return true;
 }
+// one workgroup per cell: `d` = cell_desc[blockIdx.x / PARTS], `active` / `need` = the header's active_cells / num_rendered,
+// loaded together by the caller as above
 template <int PARTS>
-__device__ __forceinline__ CellPart cell_part(const TileWs& w, uint64_t capacity) {   // blockIdx.x < cells * PARTS
+__device__ __forceinline__ CellPart cell_part(const uint4& d, uint32_t active, uint32_t need, uint64_t capacity) {
     CellPart c;
-    // the header and the cell record are independent loads: one round trip
-    const uint4 d = w.cell_desc[blockIdx.x / PARTS];
-    const uint32_t active = w.header->active_cells, need = w.header->num_rendered;
     c.cell = (int)d.x;
     c.part = (int)(blockIdx.x % PARTS);
     c.active = blockIdx.x / PARTS < active;
@@ -581,28 +590,40 @@ template <bool FOOTPRINT, int PARTS>
 __global__ __launch_bounds__(BIN_THREADS) void subtile_count_kernel(Batch<BinArgs> batch) {
     __shared__ uint32_t s_cnt[SUBS_PER_CELL];
     const BinArgs& a = batch.v[blockIdx.y];
-    const TileWs& w = a.tw;
-    const Grid& g = a.grid;
-    const BinWs& b = a.bw;
-    if ((int)blockIdx.x >= g.cells * PARTS) return;
+    // trip one: every field of the job record the working path uses (common.h: prologue discipline)
+    int cells = a.grid.cells;
+    const int gcx = a.grid.cx;
+    const uint4* __restrict__ part_desc = a.tw.part_desc;
+    const ExaRasterHeader* header = a.tw.header;
+    uint32_t* __restrict__ part_cnt = a.tw.part_cnt;
+    uint4* bucket = a.bw.bucket;
+    const Splat* __restrict__ splats = a.splats;
+    const uint64_t capacity = a.capacity;
+    EXA_TOGETHER(cells, gcx, part_desc, header, part_cnt, bucket, splats, capacity);
+    if ((int)blockIdx.x >= cells * PARTS) return;
+    // trip two: the part record and the header word.  Behind the guard above: part_desc has cells * PARTS records of THIS job
+    // (write_part_table fills all of them), the header is one per job.
+    uint4 d = uniform_word(part_desc[blockIdx.x]);
+    const uint32_t need = uniform_word(header->num_rendered);
+    EXA_TOGETHER(d.x, d.y, d.z, d.w, need);
     CellPart cp;
-    if (!cell_part_of(w, a.capacity, cp) || !cp.active) return;         // no work / empty cell: nothing to count
+    if (!cell_part_of(d, need, capacity, cp) || !cp.active) return;     // no work / empty cell: nothing to count
     const int tid = threadIdx.x;
     if (tid < SUBS_PER_CELL) s_cnt[tid] = 0u;
     __syncthreads();
-    const int csx0 = (cp.cell % g.cx) * CELL_SUBS, csy0 = (cp.cell / g.cx) * CELL_SUBS;   // cell origin in sub-tiles
+    const int csx0 = (cp.cell % gcx) * CELL_SUBS, csy0 = (cp.cell / gcx) * CELL_SUBS;   // cell origin in sub-tiles
     for (uint32_t e = cp.lo + tid; e < cp.hi; e += BIN_THREADS) {
         // ONE 16-byte load of the entry: left to itself the compiler fetched the rect words first and sank the id word
         // into the block that uses it -- behind a wait: a fourth dependent round trip in a launch that consists of four
-        uint4 en = b.bucket[e];
+        uint4 en = bucket[e];
         asm("" : "+v"(en.x) : "v"(en.y), "v"(en.z), "v"(en.w));
-        const unsigned long long mask = entry_mask<FOOTPRINT>(a.splats, en, csx0, csy0);
+        const unsigned long long mask = entry_mask<FOOTPRINT>(splats, en, csx0, csy0);
         for (unsigned long long m = mask; m; m &= m - 1)
             __hip_atomic_fetch_add(&s_cnt[__builtin_ctzll(m)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        reinterpret_cast<uint2*>(b.bucket + e)[1] = make_uint2((uint32_t)mask, (uint32_t)(mask >> 32));
+        reinterpret_cast<uint2*>(bucket + e)[1] = make_uint2((uint32_t)mask, (uint32_t)(mask >> 32));
     }
     __syncthreads();
-    if (tid < SUBS_PER_CELL) w.part_cnt[(size_t)blockIdx.x * SUBS_PER_CELL + tid] = s_cnt[tid];       // by workgroup
+    if (tid < SUBS_PER_CELL) part_cnt[(size_t)blockIdx.x * SUBS_PER_CELL + tid] = s_cnt[tid];       // by workgroup
 }
 
 template <int PARTS>
@@ -610,12 +631,27 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_bin_kernel(Batch<BinArgs>
     __shared__ uint32_t s_off[SUBS_PER_CELL];
     __shared__ uint32_t s_cnt2[SUBS_PER_CELL];
     const BinArgs& a = batch.v[blockIdx.y];
-    const TileWs& w = a.tw;
-    const Grid& g = a.grid;
-    const BinWs& b = a.bw;
-    if ((int)blockIdx.x >= g.cells * PARTS) return;
+    // trip one: every field of the job record the working path uses (common.h: prologue discipline)
+    int cells = a.grid.cells;
+    const uint4* part_desc = a.tw.part_desc;
+    const ExaRasterHeader* header = a.tw.header;
+    const uint32_t* part_cnt = a.tw.part_cnt;
+    uint2* ranges = a.tw.ranges;
+    uint8_t* cls_code = a.tw.cls_code;
+    uint32_t* cell_long = a.tw.cell_long;
+    const uint4* bucket = a.bw.bucket;
+    uint4* owner = a.bw.owner;
+    unsigned long long* keys = a.bw.keys;
+    const uint64_t capacity = a.capacity;
+    EXA_TOGETHER(cells, part_desc, header, part_cnt, ranges, cls_code, cell_long, bucket, owner, keys, capacity);
+    if ((int)blockIdx.x >= cells * PARTS) return;
+    // trip two: the part record and the header word.  Behind the guard above: part_desc has cells * PARTS records of THIS job
+    // (write_part_table fills all of them), the header is one per job.  The first entry (below) stays behind cp.overflow.
+    uint4 d = uniform_word(part_desc[blockIdx.x]);
+    const uint32_t need = uniform_word(header->num_rendered);
+    EXA_TOGETHER(d.x, d.y, d.z, d.w, need);
     CellPart cp;
-    if (!cell_part_of(w, a.capacity, cp)) return;
+    if (!cell_part_of(d, need, capacity, cp)) return;
     // empty cell: its one workgroup publishes 64 empty ranges.  So does part 0 of every cell of an OVERFLOWED render, and
     // nothing else of it runs: cell_scatter left the buckets unwritten, and the cell's entry offsets (cp.lo) count entries of
     // the render that did not fit -- they lie beyond the `capacity` entries the bucket array holds.  Until round 5 the
@@ -625,10 +661,10 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_bin_kernel(Batch<BinArgs>
     if (!cp.active || cp.overflow) {
         if (cp.part == 0) {
             if (threadIdx.x < SUBS_PER_CELL) {
-                w.ranges[cp.cell * SUBS_PER_CELL + threadIdx.x] = make_uint2(0u, 0u);
-                w.cls_code[cp.cell * SUBS_PER_CELL + threadIdx.x] = (uint8_t)0;
+                ranges[cp.cell * SUBS_PER_CELL + threadIdx.x] = make_uint2(0u, 0u);
+                cls_code[cp.cell * SUBS_PER_CELL + threadIdx.x] = (uint8_t)0;
             }
-            if (threadIdx.x == 0) w.cell_long[cp.rank] = 0u;
+            if (threadIdx.x == 0) cell_long[cp.rank] = 0u;
         }
         return;
     }
@@ -637,13 +673,13 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_bin_kernel(Batch<BinArgs>
     // was a round trip of its own (the launch consists of three)
     const uint32_t e_first = cp.lo + (uint32_t)tid;
     // (unconditional, clamped into the cell's entries: a conditional load would be waited for at the join right here)
-    const uint4 en_first = b.bucket[min(e_first, max(cp.hi, 1u) - 1u)];
+    const uint4 en_first = bucket[min(e_first, max(cp.hi, 1u) - 1u)];
     if (tid < 64) {
         uint32_t n = 0, before = 0;
         const size_t first = (size_t)blockIdx.x - (size_t)cp.part;      // the cell's parts are consecutive workgroups
 #pragma unroll 4
         for (int p = 0; p < cp.nparts; ++p) {
-            const uint32_t v = w.part_cnt[(first + p) * SUBS_PER_CELL + tid];
+            const uint32_t v = part_cnt[(first + p) * SUBS_PER_CELL + tid];
             before += p < cp.part ? v : 0u;
             n += v;
         }
@@ -654,11 +690,11 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_bin_kernel(Batch<BinArgs>
         s_cnt2[tid] = 0u;
         if (cp.part == 0) {
             const unsigned long long longer = __ballot(n > (uint32_t)BATCH);
-            if (tid == 0) w.cell_long[cp.rank] = (uint32_t)__popcll(longer);
-            w.ranges[cell * SUBS_PER_CELL + tid] = make_uint2(begin, begin + n);
-            w.cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)length_class(n);
+            if (tid == 0) cell_long[cp.rank] = (uint32_t)__popcll(longer);
+            ranges[cell * SUBS_PER_CELL + tid] = make_uint2(begin, begin + n);
+            cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)length_class(n);
             for (uint32_t bq = 0; bq + 1 < nslot; ++bq)
-                b.owner[begin / BATCH + bq] = make_uint4((uint32_t)(cell * SUBS_PER_CELL + tid) + 1u, begin, n, 0u);
+                owner[begin / BATCH + bq] = make_uint4((uint32_t)(cell * SUBS_PER_CELL + tid) + 1u, begin, n, 0u);
         }
     }
     __syncthreads();
@@ -667,11 +703,11 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_bin_kernel(Batch<BinArgs>
         for (unsigned long long m = ((unsigned long long)en.w << 32) | en.z; m; m &= m - 1) {
             const int s = __builtin_ctzll(m);
             const uint32_t r = __hip_atomic_fetch_add(&s_cnt2[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            b.keys[s_off[s] + r] = key;
+            keys[s_off[s] + r] = key;
         }
     };
     if (e_first < cp.hi) scatter(en_first);
-    for (uint32_t e = e_first + BIN_THREADS; e < cp.hi; e += BIN_THREADS) scatter(b.bucket[e]);
+    for (uint32_t e = e_first + BIN_THREADS; e < cp.hi; e += BIN_THREADS) scatter(bucket[e]);
 }
 
 // One workgroup per cell, both halves in one launch: for images with >= SINGLE_PART_CELLS cells (2048 x 2048 px) there are
@@ -680,32 +716,48 @@ template <bool FOOTPRINT>
 __global__ __launch_bounds__(BIN_THREADS) void subtile_count_bin_kernel(Batch<BinArgs> batch) {
     __shared__ uint32_t s_cnt[SUBS_PER_CELL], s_off[SUBS_PER_CELL], s_cnt2[SUBS_PER_CELL];
     const BinArgs& a = batch.v[blockIdx.y];
-    const TileWs& w = a.tw;
-    const Grid& g = a.grid;
-    const BinWs& b = a.bw;
-    if ((int)blockIdx.x >= g.cells) return;
-    const CellPart cp = cell_part<1>(w, a.capacity);
+    // trip one: every field of the job record the working path uses (common.h: prologue discipline)
+    int cells = a.grid.cells;
+    const int gcx = a.grid.cx;
+    const uint4* cell_desc = a.tw.cell_desc;
+    const ExaRasterHeader* header = a.tw.header;
+    uint2* ranges = a.tw.ranges;
+    uint8_t* cls_code = a.tw.cls_code;
+    uint32_t* cell_long = a.tw.cell_long;
+    uint4* bucket = a.bw.bucket;
+    uint4* owner = a.bw.owner;
+    unsigned long long* keys = a.bw.keys;
+    const Splat* splats = a.splats;
+    const uint64_t capacity = a.capacity;
+    EXA_TOGETHER(cells, gcx, cell_desc, header, ranges, cls_code, cell_long, bucket, owner, keys, splats, capacity);
+    if ((int)blockIdx.x >= cells) return;
+    // trip two: the cell record and the two header words.  Behind the guard above: cell_desc has `cells` records of THIS job
+    // (write_cell_order fills all of them), the header is one per job.
+    uint4 d = uniform_word(cell_desc[blockIdx.x]);
+    const uint32_t active = uniform_word(header->active_cells), need = uniform_word(header->num_rendered);
+    EXA_TOGETHER(d.x, d.y, d.z, d.w, active, need);
+    const CellPart cp = cell_part<1>(d, active, need, capacity);
     const int cell = cp.cell, tid = threadIdx.x;
     if (!cp.active) {                                                   // empty cell: 64 empty ranges
         if (tid < SUBS_PER_CELL) {
-            w.ranges[cell * SUBS_PER_CELL + tid] = make_uint2(0u, 0u);
-            w.cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)0;
+            ranges[cell * SUBS_PER_CELL + tid] = make_uint2(0u, 0u);
+            cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)0;
         }
-        if (tid == 0) w.cell_long[blockIdx.x] = 0u;
+        if (tid == 0) cell_long[blockIdx.x] = 0u;
         return;
     }
     if (tid < SUBS_PER_CELL) s_cnt[tid] = 0u;
     __syncthreads();
-    const int csx0 = (cell % g.cx) * CELL_SUBS, csy0 = (cell / g.cx) * CELL_SUBS;   // cell origin in sub-tiles
+    const int csx0 = (cell % gcx) * CELL_SUBS, csy0 = (cell / gcx) * CELL_SUBS;   // cell origin in sub-tiles
     for (uint32_t e = cp.lo + tid; e < cp.hi; e += BIN_THREADS) {
         // ONE 16-byte load of the entry: left to itself the compiler fetched the rect words first and sank the id word
         // into the block that uses it -- behind a wait: a fourth dependent round trip in a launch that consists of four
-        uint4 en = b.bucket[e];
+        uint4 en = bucket[e];
         asm("" : "+v"(en.x) : "v"(en.y), "v"(en.z), "v"(en.w));
-        const unsigned long long mask = entry_mask<FOOTPRINT>(a.splats, en, csx0, csy0);
+        const unsigned long long mask = entry_mask<FOOTPRINT>(splats, en, csx0, csy0);
         for (unsigned long long m = mask; m; m &= m - 1)
             __hip_atomic_fetch_add(&s_cnt[__builtin_ctzll(m)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        reinterpret_cast<uint2*>(b.bucket + e)[1] = make_uint2((uint32_t)mask, (uint32_t)(mask >> 32));   // read back by this thread
+        reinterpret_cast<uint2*>(bucket + e)[1] = make_uint2((uint32_t)mask, (uint32_t)(mask >> 32));   // read back by this thread
     }
     __syncthreads();
     if (tid < 64) {
@@ -716,20 +768,20 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_count_bin_kernel(Batch<Bi
         s_off[tid] = begin;
         s_cnt2[tid] = 0u;
         const unsigned long long longer = __ballot(n > (uint32_t)BATCH);
-        if (tid == 0) w.cell_long[blockIdx.x] = (uint32_t)__popcll(longer);
-        w.ranges[cell * SUBS_PER_CELL + tid] = make_uint2(begin, begin + n);
-        w.cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)length_class(n);
+        if (tid == 0) cell_long[blockIdx.x] = (uint32_t)__popcll(longer);
+        ranges[cell * SUBS_PER_CELL + tid] = make_uint2(begin, begin + n);
+        cls_code[cell * SUBS_PER_CELL + tid] = (uint8_t)length_class(n);
         for (uint32_t bq = 0; bq + 1 < nslot; ++bq)
-            b.owner[begin / BATCH + bq] = make_uint4((uint32_t)(cell * SUBS_PER_CELL + tid) + 1u, begin, n, 0u);
+            owner[begin / BATCH + bq] = make_uint4((uint32_t)(cell * SUBS_PER_CELL + tid) + 1u, begin, n, 0u);
     }
     __syncthreads();
     for (uint32_t e = cp.lo + tid; e < cp.hi; e += BIN_THREADS) {
-        const uint4 en = b.bucket[e];
+        const uint4 en = bucket[e];
         const unsigned long long key = ((unsigned long long)en.y << 32) | en.x;
         for (unsigned long long m = ((unsigned long long)en.w << 32) | en.z; m; m &= m - 1) {
             const int s = __builtin_ctzll(m);
             const uint32_t r = __hip_atomic_fetch_add(&s_cnt2[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            b.keys[s_off[s] + r] = key;
+            keys[s_off[s] + r] = key;
         }
     }
 }

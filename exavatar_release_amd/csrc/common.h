@@ -43,6 +43,75 @@ inline Batch<T> make_batch(const T* a, int K) {          // unused slots repeat 
     return b;
 }
 
+// Prologue discipline of the step kernels.  A job record is ~300 bytes of kernel arguments over five 64-byte lines, and
+// left to itself the compiler requests every field with an s_load right where it is first used, behind the branch that
+// needed the previous one.  `s_waitcnt lgkmcnt(0)` is all-or-nothing for scalar loads (they return out of order), so every
+// such wait is a full serial round trip, and a kernel written the plain way waits four to eight times in front of its first
+// vector load where the data dependences ask for two (tools/prologue_trips.py prints the counts from the ISA).  The kernels
+// whose workgroups all work -- cell_scatter, subtile_count, subtile_bin, subtile_count_bin, render_fwd, render_bwd,
+// preprocess_bwd -- therefore open with
+//   trip one   every field of the job record that the working path uses, read into locals by plain C++ loads, and ONE
+//              EXA_TOGETHER(guard, ...) naming them all: an empty asm statement that needs all its operands in scalar
+//              registers, so the loads leave back to back in front of a single wait;
+//   trip two   the descriptor words that depend on trip one and the block index only (header word, part_desc / cell_desc /
+//              slots record, the backward's order words, the background), again behind one EXA_TOGETHER.
+// preprocess_fwd and the sort kernels do NOT: measured, it bought the first nothing and cost sort_subtiles, most of whose
+// workgroups read one header word and leave, 0.6 us (profiles/prologue_trips.md).
+// The loads themselves stay C++: the compiler does not count a load inside an asm statement in lgkmcnt and may reuse its
+// destination while it is in flight.  NO load moves above the guard that makes its address valid; each hoisted load says
+// in a comment why its address is in range for every workgroup of the grid.  Operands must be wave-uniform AND in scalar
+// registers: a word loaded in trip two goes through uniform_word() (below), which costs nothing behind an s_load and keeps
+// the statement compiling where the compiler chose a vector load.
+// The statement is NOT volatile and has no memory clobber (a volatile one counts as a store to anything, and every uniform
+// load behind it turns from an s_load into a vector load); what keeps it alive and in place is its first operand, read AND
+// written: name the value the next branch tests (a mutable local) first.  At most 24 values behind the guard (an asm
+// statement takes 30 operands); more is a compile error that says so.
+#define EXA_TG_1(a) "s"(a)
+#define EXA_TG_2(a, ...) "s"(a), EXA_TG_1(__VA_ARGS__)
+#define EXA_TG_3(a, ...) "s"(a), EXA_TG_2(__VA_ARGS__)
+#define EXA_TG_4(a, ...) "s"(a), EXA_TG_3(__VA_ARGS__)
+#define EXA_TG_5(a, ...) "s"(a), EXA_TG_4(__VA_ARGS__)
+#define EXA_TG_6(a, ...) "s"(a), EXA_TG_5(__VA_ARGS__)
+#define EXA_TG_7(a, ...) "s"(a), EXA_TG_6(__VA_ARGS__)
+#define EXA_TG_8(a, ...) "s"(a), EXA_TG_7(__VA_ARGS__)
+#define EXA_TG_9(a, ...) "s"(a), EXA_TG_8(__VA_ARGS__)
+#define EXA_TG_10(a, ...) "s"(a), EXA_TG_9(__VA_ARGS__)
+#define EXA_TG_11(a, ...) "s"(a), EXA_TG_10(__VA_ARGS__)
+#define EXA_TG_12(a, ...) "s"(a), EXA_TG_11(__VA_ARGS__)
+#define EXA_TG_13(a, ...) "s"(a), EXA_TG_12(__VA_ARGS__)
+#define EXA_TG_14(a, ...) "s"(a), EXA_TG_13(__VA_ARGS__)
+#define EXA_TG_15(a, ...) "s"(a), EXA_TG_14(__VA_ARGS__)
+#define EXA_TG_16(a, ...) "s"(a), EXA_TG_15(__VA_ARGS__)
+#define EXA_TG_17(a, ...) "s"(a), EXA_TG_16(__VA_ARGS__)
+#define EXA_TG_18(a, ...) "s"(a), EXA_TG_17(__VA_ARGS__)
+#define EXA_TG_19(a, ...) "s"(a), EXA_TG_18(__VA_ARGS__)
+#define EXA_TG_20(a, ...) "s"(a), EXA_TG_19(__VA_ARGS__)
+#define EXA_TG_21(a, ...) "s"(a), EXA_TG_20(__VA_ARGS__)
+#define EXA_TG_22(a, ...) "s"(a), EXA_TG_21(__VA_ARGS__)
+#define EXA_TG_23(a, ...) "s"(a), EXA_TG_22(__VA_ARGS__)
+#define EXA_TG_24(a, ...) "s"(a), EXA_TG_23(__VA_ARGS__)
+#define EXA_TG_TOO_MANY(...) "s"(EXA_TOGETHER_takes_at_most_24_values_behind_the_guard)
+#define EXA_TG_PICK(_1, _2, _3, _4, _5, _6, _7, _8, _9, _10, _11, _12, _13, _14, _15, _16, _17, _18, _19, _20, _21, _22, _23, _24, \
+                    _25, _26, _27, _28, _29, _30, _31, _32, N, ...) N
+#define EXA_TOGETHER(guard, ...)                                                                                            \
+    asm("" : "+s"(guard)                                                                                                    \
+        : EXA_TG_PICK(__VA_ARGS__, EXA_TG_TOO_MANY, EXA_TG_TOO_MANY, EXA_TG_TOO_MANY, EXA_TG_TOO_MANY, EXA_TG_TOO_MANY,      \
+                      EXA_TG_TOO_MANY, EXA_TG_TOO_MANY, EXA_TG_TOO_MANY, EXA_TG_24, EXA_TG_23, EXA_TG_22, EXA_TG_21,         \
+                      EXA_TG_20, EXA_TG_19, EXA_TG_18, EXA_TG_17, EXA_TG_16, EXA_TG_15, EXA_TG_14, EXA_TG_13, EXA_TG_12,     \
+                      EXA_TG_11, EXA_TG_10, EXA_TG_9, EXA_TG_8, EXA_TG_7, EXA_TG_6, EXA_TG_5, EXA_TG_4, EXA_TG_3, EXA_TG_2,  \
+                      EXA_TG_1)(__VA_ARGS__))
+
+// A wave-uniform 32-bit word where EXA_TOGETHER needs it: in a scalar register.  Behind an s_load this is nothing (the
+// compiler folds the v_readfirstlane of a scalar away).  Whether a uniform load IS an s_load is the compiler's choice: a
+// store, an atomic or a clock read in front of it (the probe builds, -DEXA_PROBE_*, read the clock in front of their
+// descriptor loads) counts as a possible write to the word, the load then comes back through the vector path, and without
+// this the "s" operands are a compile error.  Every word of a trip two passes through it.
+__device__ __forceinline__ uint32_t uniform_word(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float uniform_word(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ uint4 uniform_word(const uint4& v) {
+    return make_uint4(uniform_word(v.x), uniform_word(v.y), uniform_word(v.z), uniform_word(v.w));
+}
+
 constexpr float NEAR_CULL = 0.2f;
 constexpr float LOWPASS = 0.3f;
 constexpr float ALPHA_MAX = 0.99f;
@@ -154,11 +223,13 @@ struct TileWs {
                                       //              tiles_touched, summed: header.num_tile_instances)
     uint32_t* chunk_off;              // [chunks]     exclusive prefix of chunk_inst
     uint4* cell_desc;                 // [cells]      cells by descending instance count (heavy work first):
-                                      //              {cell, first entry, end entry, first instance slot * 64} -- ONE load
-                                      //              gives a per-cell workgroup its work
+                                      //              {cell, first entry, end entry, first instance slot * 64} -- ONE record
+                                      //              gives a per-cell workgroup its work (requested with the header words, in
+                                      //              the second trip of the kernel's prologue: EXA_TOGETHER above)
     uint2* ranges;                    // [subtiles]   [begin, end) into the instance arrays, cell-major
-    uint4* slots;                     // [subtiles]   launch-order records {begin, end, st, 0}: ONE load gives a
-                                      //              per-pixel-kernel workgroup everything it needs
+    uint4* slots;                     // [subtiles]   launch-order records {begin, end, st, 0}: ONE record gives a
+                                      //              per-pixel-kernel workgroup everything it needs (the second trip of its
+                                      //              prologue; the first is its job record)
     uint2* fwd_exit;                  // [subtiles]   {list length, batches the forward entered}
     uint32_t* cell_long;              // [cells]      by rank in cell_desc: number of the cell's lists longer than 64 keys
     uint32_t* part_cnt;               // [cells * BIN_PARTS][64]  entries per sub-tile counted by each workgroup of the
@@ -388,8 +459,12 @@ struct RenderFwdArgs {
     const float* src_color; const float* src_depth; const float* src_alpha; const float* src_bg;
 };
 // Composite renders: may the pixels of source A stand in for sub-tiles without B entries?  (Wave-uniform: six scalar loads.)
+// (bg0 .. bg2: the words of the render's own background, which the blend has in registers from its prologue)
+__device__ __forceinline__ bool reuse_a_pixels(const float* src_color, const float* src_bg, float bg0, float bg1, float bg2) {
+    return src_color != nullptr && src_bg[0] == bg0 && src_bg[1] == bg1 && src_bg[2] == bg2;
+}
 __device__ __forceinline__ bool reuse_a_pixels(const float* src_color, const float* src_bg, const float* bg) {
-    return src_color != nullptr && src_bg[0] == bg[0] && src_bg[1] == bg[1] && src_bg[2] == bg[2];
+    return reuse_a_pixels(src_color, src_bg, bg[0], bg[1], bg[2]);
 }
 hipError_t launch_sort_subtiles(const RenderFwdArgs* a, int K, hipStream_t s);
 // Composite of two finished renders (compose.hip): ranges / header / launch order / zero-fill, then the merged id lists

@@ -281,11 +281,19 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
     const PreprocessBwdArgs& out = batch.v[SUM ? 0 : blockIdx.y];
     const int vw = VW > 1 ? (int)(blockDim.x >> 6) : 1;         // views per workgroup row (VW > 1)
     const int GPB = VW > 1 ? 64 : BLOCK;                        // Gaussians per workgroup
-    if ((int)(blockIdx.x * GPB) >= out.P) return;               // workgroup-uniform
+    // trip one (common.h: prologue discipline): the guard's word and, with it, the three pointers behind the loads that gate
+    // the gather.  One job per workgroup (!SUM) only: a summed batch takes them from the record of each view in turn.
+    int P_guard = out.P;
+    const Splat* splats0 = out.splats;
+    const int32_t* radii0 = out.radii;
+    const ExaRasterHeader* header0 = out.header;
+    const int gf = PREFIX ? out.grad_first : 0;
+    if (!SUM && PREFIX) EXA_TOGETHER(P_guard, splats0, radii0, header0, gf);
+    else if (!SUM) EXA_TOGETHER(P_guard, splats0, radii0, header0);
+    if ((int)(blockIdx.x * GPB) >= P_guard) return;             // workgroup-uniform
     // constant prefix (ExaRasterBackwardJob.grad_first): Gaussians below gf are inputs only -- no chain rule, no output
     // row (row = idx - gf).  A workgroup of constants leaves at once; in the boundary workgroup they stay in the wave
     // for the cooperative gather below but are neither `vis` nor `valid`.
-    const int gf = PREFIX ? out.grad_first : 0;
     if (PREFIX && (int)((blockIdx.x + 1) * GPB) <= gf) return;  // workgroup-uniform
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #ifdef EXA_PROBE_PBWD      // probe build only (tools/gpu_pbwd_phases.py): phases of every wave on the 100 MHz clock
@@ -325,9 +333,9 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
         const float* __restrict__ p = a.projmatrix;
         // What gates the gather goes first and leaves together: row 3 of the splat record, the radius, the overflow word
         // (all three unconditional: behind `valid && ...` the radius was requested only after the overflow word had arrived)
-        const uint4 r3 = reinterpret_cast<const uint4*>(a.splats + idc)[3];
-        const int rad = a.radii[idc];
-        const uint32_t ovf = a.header->overflow;
+        const uint4 r3 = reinterpret_cast<const uint4*>((SUM ? a.splats : splats0) + idc)[3];
+        const int rad = (SUM ? a.radii : radii0)[idc];
+        const uint32_t ovf = (SUM ? a.header : header0)->overflow;
         // an overflowed forward left no lists behind: every gradient of that view is zero (the overflow itself is
         // reported to the host through the header, include/exa_raster.h)
         const bool vis = valid && ovf == 0u && rad > 0;

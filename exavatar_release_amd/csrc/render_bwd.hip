@@ -178,7 +178,37 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
     __shared__ __attribute__((aligned(16))) float s_x_[WPB][XLayout<GC>::FLOATS];   // {aG, w}[pixel group][splat][pixel of the group]
 
     const RenderBwdArgs& a = batch.v[blockIdx.y];
-    const uint32_t nslots = (uint32_t)(a.capacity / BATCH);
+    // trip one: every field of the job record the working path uses (common.h: prologue discipline), and the launch height
+    // with them -- gridDim.y lives in the hidden arguments, a line far behind the job records
+    uint64_t capacity = a.capacity;
+    const uint32_t gdy = gridDim.y;
+    const int gW = a.grid.W, gH = a.grid.H, gcx = a.grid.cx, P = a.P;
+    const uint32_t* bwd_meta = a.tw.bwd_meta;
+    const uint4* bucket = a.bw.bucket;
+    const uint4* owner = a.bw.owner;
+    const unsigned long long* bmask = a.bw.bmask;
+    const uint32_t* sorted = a.bw.sorted;
+    const float* ckpt = a.bw.ckpt;
+    const Splat* splats = a.splats;
+    const float* __restrict__ bg = a.bg;
+    const float* dL_dcolor_arg = a.dL_dcolor;
+    const float* const* dL_dcolor_ind = a.dL_dcolor_ind;
+    const float* dL_ddepth = a.dL_ddepth;
+    const float* dL_dalpha = a.dL_dalpha;
+    float4* __restrict__ prec = a.partials.rec;
+    uint8_t* __restrict__ touched = a.bw.touched;
+    const Splat* splats2 = a.splats2;                            // (PREFIX only, with the next two)
+    const int P2 = a.P2;
+    const uint32_t grad_first = PREFIX ? (uint32_t)a.grad_first : 0u;
+    if (PREFIX)
+        EXA_TOGETHER(capacity, gdy, gW, gH, gcx, P, bwd_meta, bucket, owner, bmask, sorted, ckpt, splats, bg, dL_dcolor_arg,
+                     dL_dcolor_ind, dL_ddepth, dL_dalpha, prec, touched, splats2, P2, grad_first);
+    else
+        EXA_TOGETHER(capacity, gdy, gW, gH, gcx, P, bwd_meta, bucket, owner, bmask, sorted, ckpt, splats, bg, dL_dcolor_arg,
+                     dL_dcolor_ind, dL_ddepth, dL_dalpha, prec, touched);
+    Grid grid;                                                   // (decode_subtile reads cx only)
+    grid.W = gW; grid.H = gH; grid.cx = gcx;
+    const uint32_t nslots = (uint32_t)(capacity / BATCH);
     const int lane = threadIdx.x & 63;
     const int wv = WPB > 1 ? (int)(threadIdx.x >> 6) : 0;
     const uint32_t wg = (uint32_t)blockIdx.x * WPB + (uint32_t)wv;        // this wave's position in the launch
@@ -191,31 +221,30 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
         __device__ ~TL() { if (lane == 0 && 2 * blockIdx.x + 1 < (uint32_t)(a.grid.cells * BIN_PARTS * SUBS_PER_CELL)) {
             a.tw.part_cnt[2 * blockIdx.x] = (uint32_t)t0; a.tw.part_cnt[2 * blockIdx.x + 1] = (uint32_t)wall_clock64(); } } } tl{a, (unsigned long long)wall_clock64(), lane};
 #endif
-    const float* __restrict__ bg = a.bg;
     // (graph replays with a new gradient tensor per iteration: include/exa_raster.h, dL_dcolor_indirect; a scalar load)
     // (the cast matters: a pointer LOADED from memory is generic to the compiler, and flat loads also count on lgkmcnt --
     //  every LDS / scalar wait behind them would wait for HBM)
     typedef const float __attribute__((address_space(1)))* gfloat_ptr;
     typedef const unsigned long long __attribute__((address_space(4)))* table_ptr;       // constant: a scalar load
-    const gfloat_ptr dL_dcolor = a.dL_dcolor_ind ? (gfloat_ptr)(*(table_ptr)(unsigned long long)a.dL_dcolor_ind)
-                                                 : (gfloat_ptr)a.dL_dcolor;
-    float4* __restrict__ prec = a.partials.rec;
-    uint8_t* __restrict__ touched = a.bw.touched;
+    // trip two, with the order words below: the indirect gradient pointer (behind its own null test: a plain render has no
+    // table) and the background (`bg` is never null, checked by the C ABI, and holds three floats)
+    const gfloat_ptr dL_dcolor = dL_dcolor_ind ? (gfloat_ptr)(*(table_ptr)(unsigned long long)dL_dcolor_ind)
+                                               : (gfloat_ptr)dL_dcolor_arg;
+    const float bg0 = uniform_word(bg[0]), bg1 = uniform_word(bg[1]), bg2 = uniform_word(bg[2]);
 
     auto load_hdr = [&](uint32_t slot) -> BwdHdr {
         BwdHdr h = {0u, 0u, 0u, 0u, 0u, 0u};
         if (slot < nslots) {
-            const uint4 own = a.bw.owner[slot];
-            const unsigned long long bm = a.bw.bmask[slot];
-            h.id = a.bw.sorted[(size_t)slot * BATCH + lane];
+            const uint4 own = owner[slot];
+            const unsigned long long bm = bmask[slot];
+            h.id = sorted[(size_t)slot * BATCH + lane];
             h.st1 = own.x; h.begin = own.y; h.n = own.z;
             h.bm_lo = (uint32_t)bm; h.bm_hi = (uint32_t)(bm >> 32);
         }
         return h;
     };
-    const uint32_t grad_first = PREFIX ? (uint32_t)a.grad_first : 0u;
     // composite render (compose.hip): ids of two sources, bit 31 = source B = the trainable Gaussians; A is constant
-    const bool two = PREFIX && a.splats2 != nullptr;
+    const bool two = PREFIX && splats2 != nullptr;
     auto trainable = [&](uint32_t id) -> bool { return two ? (id & SRC_B) != 0u : id >= grad_first; };
     auto is_active = [&](const BwdHdr& h) -> bool {              // wave-uniform
         uint32_t lo = __builtin_amdgcn_readfirstlane(h.bm_lo), hi = __builtin_amdgcn_readfirstlane(h.bm_hi);
@@ -241,14 +270,14 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
         const int st = (int)__builtin_amdgcn_readfirstlane(h.st1) - 1;
         const int n = (int)__builtin_amdgcn_readfirstlane(h.n);
         const int b0 = (int)(__builtin_amdgcn_readfirstlane(h.begin) / BATCH);
-        const SubTile sub = decode_subtile(st, a.grid);
+        const SubTile sub = decode_subtile(st, grid);
         const bool flagged = (((lane < 32 ? bm_lo : bm_hi) >> (lane & 31)) & 1u) != 0u;
         if (flagged) {
-            const Splat* base = a.splats;
-            uint32_t idx = h.id, last = (uint32_t)(a.P - 1);
+            const Splat* base = splats;
+            uint32_t idx = h.id, last = (uint32_t)(P - 1);
             if (two) {
                 idx = h.id & ~SRC_B;
-                if (h.id & SRC_B) { base = a.splats2; last = (uint32_t)(a.P2 - 1); }
+                if (h.id & SRC_B) { base = splats2; last = (uint32_t)(P2 - 1); }
             }
             const float4* rec = reinterpret_cast<const float4*>(base + min(idx, last));
             p.r0 = *reinterpret_cast<const float2*>(rec); p.r1 = rec[1]; p.r2 = rec[2];
@@ -258,19 +287,19 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
             if (PREFIX && !trainable(h.id)) p.pslot = NO_SLOT;
         }
         // state at the START of this batch and at the forward's exit (the sub-tile's end slot)
-        const float* cf = a.bw.ckpt + (size_t)(b0 + (n + BATCH - 1) / BATCH) * (5 * 64) + lane;
-        const float* cs = a.bw.ckpt + (size_t)slot * (5 * 64) + lane;
+        const float* cf = ckpt + (size_t)(b0 + (n + BATCH - 1) / BATCH) * (5 * 64) + lane;
+        const float* cs = ckpt + (size_t)slot * (5 * 64) + lane;
         if ((int)slot > b0) { p.cs0 = cs[0]; p.cs1 = cs[64]; p.cs2 = cs[128]; p.cs3 = cs[192]; p.cs4 = HAS_DEPTH ? cs[256] : 0.f; }
         p.cf0 = cf[0]; p.cf1 = cf[64]; p.cf2 = cf[128]; p.cf3 = cf[192]; p.cf4 = HAS_DEPTH ? cf[256] : 0.f;
         const int pxi = sub.ox + (lane & 7), pyi = sub.oy + (lane >> 3);
-        if (pxi < a.grid.W && pyi < a.grid.H) {
-            const size_t HW = (size_t)a.grid.W * a.grid.H;
-            const size_t pix = (size_t)pyi * a.grid.W + pxi;
+        if (pxi < gW && pyi < gH) {
+            const size_t HW = (size_t)gW * gH;
+            const size_t pix = (size_t)pyi * gW + pxi;
             p.gr = dL_dcolor[pix];
             p.gg = dL_dcolor[HW + pix];
             p.gb = dL_dcolor[2 * HW + pix];
-            if (HAS_DEPTH && a.dL_ddepth) p.gd = a.dL_ddepth[pix];
-            if (a.dL_dalpha) p.ga = a.dL_dalpha[pix];
+            if (HAS_DEPTH && dL_ddepth) p.gd = dL_ddepth[pix];
+            if (dL_dalpha) p.ga = dL_dalpha[pix];
         }
         return p;
     };
@@ -286,11 +315,15 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
     // several jobs balances itself, and the extra dependent load cost 2.5 % there: 8 490 -> 8 260 it/s at K = 8; the three plain
     // renders of the five-render iteration, K = 3: 0.755 -> 0.767 ms per iteration with the order) keep the slot order.
     uint32_t first_slot = wg * SPW;
-    if (SPW == 1 && gridDim.y == 1) {
-        const uint32_t m0 = a.tw.bwd_meta[0], m1 = a.tw.bwd_meta[1], magic = a.tw.bwd_meta[2];
-        // (requested together with the three words above: one trip; a composite's bin workspace has no bucket array)
-        const uint32_t mapped = a.bw.bucket ? reinterpret_cast<const uint32_t*>(a.bw.bucket)[min(wg, nslots - 1u)] : 0u;
-        if (magic == BWD_ORDER_MAGIC && a.bw.bucket) {
+    if (SPW == 1 && gdy == 1) {
+        uint32_t m0 = uniform_word(bwd_meta[0]);
+        const uint32_t m1 = uniform_word(bwd_meta[1]), magic = uniform_word(bwd_meta[2]);
+        // (requested together with the three words above: one trip; a composite's bin workspace has no bucket array.  The
+        //  index is clamped into the `capacity` words the dead bucket array certainly holds: 16 bytes per entry.)
+        uint32_t mapped = bucket ? reinterpret_cast<const uint32_t*>(bucket)[min(wg, nslots - 1u)] : 0u;
+        if (WPB == 1) mapped = uniform_word(mapped);
+        if (WPB == 1) EXA_TOGETHER(m0, m1, magic, mapped, bg0, bg1, bg2);      // (WPB > 1: wg differs between the waves)
+        if (magic == BWD_ORDER_MAGIC && bucket) {
             if (wg >= m0 + m1) return;
             first_slot = mapped;
         }
@@ -316,9 +349,9 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
     const bool flagged = (((lane < 32 ? bm_lo : bm_hi) >> (lane & 31)) & 1u) != 0u;
     const int below = mask_rank(bm_lo, bm_hi);
     const int dst = flagged ? below : cnt + (lane - below);     // a permutation of 0..63: blended entries first, in order
-    const SubTile sub = decode_subtile(st, a.grid);
+    const SubTile sub = decode_subtile(st, grid);
     const int pxi = sub.ox + (lane & 7), pyi = sub.oy + (lane >> 3);
-    const bool inside = pxi < a.grid.W && pyi < a.grid.H;
+    const bool inside = pxi < gW && pyi < gH;
     const float fx = (float)pxi, fy = (float)pyi;
     const float gr = p0.gr, gg = p0.gg, gb = p0.gb, gd = p0.gd, ga = p0.ga;
 
@@ -334,7 +367,7 @@ __global__ __launch_bounds__(RBLOCK * WPB) void render_bwd_kernel(Batch<RenderBw
     }
     const float T_final = p0.cf0;
     // d/d(alpha_i) of [T_final * bg . g] and of [ga * (1 - T_final)]:  (T_final / (1 - alpha_i)) * (ga - bg.g)
-    const float tail = T_final * (ga - (bg[0] * gr + bg[1] * gg + bg[2] * gb));
+    const float tail = T_final * (ga - (bg0 * gr + bg1 * gg + bg2 * gb));
     float R = (p0.cf1 - sr) * gr + (p0.cf2 - sg) * gg + (p0.cf3 - sb) * gb - tail;
     if (HAS_DEPTH) R = fmaf(p0.cf4 - sd, gd, R);
     wave_lds_fence();

@@ -525,7 +525,9 @@ __global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(6, 6))) 
     if (blockIdx.x == ORDER_WGS && tid == 0 && (uint64_t)a.tw.header->num_rendered > a.capacity) a.tw.header->overflow = 1u;
     // Only the sub-tiles of the ACTIVE cells hold lists (cell_desc lists those cells first, heaviest first;
     // header.active_cells counts them): an avatar view has ~3 800 non-empty lists in 16 384 sub-tiles, and the
-    // workgroups of the empty ones leave after ONE scalar load instead of two dependent vector loads.  (A
+    // workgroups of the empty ones leave after ONE scalar load instead of two dependent vector loads (one load of DATA: in the
+    // ISA four serial scalar trips lead up to it, and grouping them as the other step kernels do -- common.h, prologue
+    // discipline -- made this launch 0.6 us slower, profiles/prologue_trips.md: the parent's prologue stays).  (A
     // grid-stride loop over the active sub-tiles with a smaller grid cost 2.5x the registers and ran slower; so did, in
     // round 3, a grid over 3/8 of the cells whose workgroups continue with further lists only when more cells are
     // active: the loop around the sorts spills on the hot path at six waves per SIMD -- 13.4 -> 48.9 us -- although the
@@ -583,40 +585,66 @@ __global__ __launch_bounds__(RBLOCK) void render_fwd_kernel(Batch<RenderFwdArgs>
     __shared__ BatchLds s_b;
 
     const RenderFwdArgs& a = batch.v[blockIdx.y];
-    if ((int)blockIdx.x >= a.grid.subtiles) return;
+    // trip one: every field of the job record the working path uses (common.h: prologue discipline); the output pointers too:
+    // requested where they are used they were one more serial trip at the end of every wave, and the background behind them
+    int subtiles = a.grid.subtiles;
+    const int gW = a.grid.W, gH = a.grid.H, gcx = a.grid.cx;
+    const uint4* __restrict__ slots = a.tw.slots;
+    const Splat* __restrict__ splats = a.splats;
+    const uint32_t* __restrict__ sorted_all = a.bw.sorted;
+    float* ckpt_all = a.bw.ckpt;
+    unsigned long long* bmask = a.bw.bmask;                      // (STORE only: dead otherwise, as fwd_exit)
+    uint2* fwd_exit = a.tw.fwd_exit;
+    const float* __restrict__ bg = a.bg;
+    float* out_color = a.out_color; float* out_depth = a.out_depth; float* out_alpha = a.out_alpha;
+    const uint2* ranges = a.tw.ranges;                           // (TWO only, with the next five)
+    const Splat* __restrict__ splats2 = a.splats2;
+    const float* src_color = a.src_color; const float* src_depth = a.src_depth; const float* src_alpha = a.src_alpha;
+    const float* src_bg = a.src_bg;
+    if (TWO)
+        EXA_TOGETHER(subtiles, gW, gH, gcx, slots, splats, sorted_all, ckpt_all, bmask, fwd_exit, bg, out_color, out_depth, out_alpha,
+                     ranges, splats2, src_color, src_depth, src_alpha, src_bg);
+    else
+        EXA_TOGETHER(subtiles, gW, gH, gcx, slots, splats, sorted_all, ckpt_all, bmask, fwd_exit, bg, out_color, out_depth, out_alpha);
+    if ((int)blockIdx.x >= subtiles) return;
     const int lane = threadIdx.x;
 #ifdef EXA_PROBE_FWD       // probe build only (tools/gpu_fwd_timeline.py): start / end of every wave on the chip-wide 100 MHz clock
     const unsigned long long t0 = wall_clock64();
 #endif
-    const uint4 slot = a.tw.slots[blockIdx.x];                  // {begin, end, st, 0}; empty range on overflow
-    const SubTile sub = decode_subtile((int)slot.z, a.grid);
+    // trip two: the launch record and the background.  Behind the guard above: order_slots writes one record for every
+    // sub-tile of THIS job (`subtiles` of them); `bg` is never null (checked by the C ABI) and holds three floats.
+    uint4 slot = uniform_word(slots[blockIdx.x]);                           // {begin, end, st, 0}; empty range on overflow
+    const float bg0 = uniform_word(bg[0]), bg1 = uniform_word(bg[1]), bg2 = uniform_word(bg[2]);
+    EXA_TOGETHER(slot.z, slot.x, slot.y, slot.w, bg0, bg1, bg2);   // (slot.w named: its register is not free for bg2 while the load flies)
+    Grid grid;                                                   // (decode_subtile reads cx only)
+    grid.W = gW; grid.H = gH; grid.cx = gcx;
+    const SubTile sub = decode_subtile((int)slot.z, grid);
     const int st = sub.st;
-    if (sub.ox >= a.grid.W || sub.oy >= a.grid.H) return;       // padding sub-tile of a border cell
+    if (sub.ox >= gW || sub.oy >= gH) return;                   // padding sub-tile of a border cell
     const int pxi = sub.ox + (lane & 7), pyi = sub.oy + (lane >> 3);
-    const bool inside = pxi < a.grid.W && pyi < a.grid.H;
+    const bool inside = pxi < gW && pyi < gH;
     const float fx = (float)pxi, fy = (float)pyi;
-    const uint2 range = TWO ? a.tw.ranges[slot.z] : make_uint2(slot.x, slot.y);
+    const uint2 range = TWO ? ranges[slot.z] : make_uint2(slot.x, slot.y);
     const int n = (int)(range.y - range.x);
-    if (TWO && n == 0 && reuse_a_pixels(a.src_color, a.src_bg, a.bg)) {
+    if (TWO && n == 0 && reuse_a_pixels(src_color, src_bg, bg0, bg1, bg2)) {
         // no entry of B in this sub-tile (compose.hip emptied its list): the composite's pixels are source A's own, which
         // blended exactly the list the merge would have produced, over an equal background
         if (inside) {
-            const size_t HW = (size_t)a.grid.W * a.grid.H, pix = (size_t)pyi * a.grid.W + pxi;
-            const float c0 = a.src_color[pix], c1 = a.src_color[HW + pix], c2 = a.src_color[2 * HW + pix];
-            const float d = a.src_depth[pix], al = a.src_alpha[pix];
-            a.out_color[pix] = c0; a.out_color[HW + pix] = c1; a.out_color[2 * HW + pix] = c2;
-            a.out_depth[pix] = d; a.out_alpha[pix] = al;
+            const size_t HW = (size_t)gW * gH, pix = (size_t)pyi * gW + pxi;
+            const float c0 = src_color[pix], c1 = src_color[HW + pix], c2 = src_color[2 * HW + pix];
+            const float d = src_depth[pix], al = src_alpha[pix];
+            out_color[pix] = c0; out_color[HW + pix] = c1; out_color[2 * HW + pix] = c2;
+            out_depth[pix] = d; out_alpha[pix] = al;
         }
-        if (STORE && lane == 0) a.tw.fwd_exit[st] = make_uint2(0u, 0u);
+        if (STORE && lane == 0) fwd_exit[st] = make_uint2(0u, 0u);
         return;
     }
 
     float T = inside ? 1.0f : 0.0f, Tdead = 1.0f;              // blend.h: T = 0 once the pixel has stopped, Tdead = what it stopped with
     v2f Crg = {0.f, 0.f}, Cbd = {0.f, 0.f};                     // (r, g) and (b, depth) accumulators
-    const Splat* __restrict__ splats = a.splats;
-    const uint32_t* __restrict__ sorted = a.bw.sorted + range.x;
+    const uint32_t* __restrict__ sorted = sorted_all + range.x;
     auto record = [&](uint32_t id) -> const float4* {
-        if (TWO) return reinterpret_cast<const float4*>(((id & SRC_B) ? a.splats2 : splats) + (id & ~SRC_B));
+        if (TWO) return reinterpret_cast<const float4*>(((id & SRC_B) ? splats2 : splats) + (id & ~SRC_B));
         return reinterpret_cast<const float4*>(splats + id);
     };
 
@@ -634,7 +662,7 @@ __global__ __launch_bounds__(RBLOCK) void render_fwd_kernel(Batch<RenderFwdArgs>
     }
     // training: per-pixel state at the START of every batch slot (and at the exit), so that the backward
     // pass can give every batch its own wave (render_bwd.hip).  A stopped pixel is stored as -T.
-    float* ckpt = a.bw.ckpt + (size_t)(range.x / BATCH) * (5 * 64) + lane;
+    float* ckpt = ckpt_all + (size_t)(range.x / BATCH) * (5 * 64) + lane;
     int entered = 0;
     for (int base = 0; base < n; base += 64) {
         if (__all(T == 0.0f)) break;
@@ -721,24 +749,23 @@ __global__ __launch_bounds__(RBLOCK) void render_fwd_kernel(Batch<RenderFwdArgs>
             opsA = load_ops4(s_b, (k + 8) & 63);
             if (group4(opsB, k + 4)) break;
         }
-        if (STORE && lane == 0) a.bw.bmask[range.x / BATCH + (uint32_t)(entered - 1)] = blended;
+        if (STORE && lane == 0) bmask[range.x / BATCH + (uint32_t)(entered - 1)] = blended;
         wave_lds_fence();
     }
 
     // ---- outputs ---------------------------------------------------------------------------------
-    const size_t HW = (size_t)a.grid.W * a.grid.H;
+    const size_t HW = (size_t)gW * gH;
     if (inside) {
-        const size_t pix = (size_t)pyi * a.grid.W + pxi;
-        const float* __restrict__ bg = a.bg;
+        const size_t pix = (size_t)pyi * gW + pxi;
         const float Tf = T > 0.0f ? T : Tdead;
-        a.out_color[pix] = Crg.x + Tf * bg[0];
-        a.out_color[HW + pix] = Crg.y + Tf * bg[1];
-        a.out_color[2 * HW + pix] = Cbd.x + Tf * bg[2];
-        a.out_depth[pix] = Cbd.y;
-        a.out_alpha[pix] = 1.0f - Tf;
+        out_color[pix] = Crg.x + Tf * bg0;
+        out_color[HW + pix] = Crg.y + Tf * bg1;
+        out_color[2 * HW + pix] = Cbd.x + Tf * bg2;
+        out_depth[pix] = Cbd.y;
+        out_alpha[pix] = 1.0f - Tf;
     }
     if (STORE) {
-        if (lane == 0) a.tw.fwd_exit[st] = make_uint2((uint32_t)n, (uint32_t)entered);
+        if (lane == 0) fwd_exit[st] = make_uint2((uint32_t)n, (uint32_t)entered);
 #ifdef EXA_PROBE_FWD
         if (lane == 0) {       // part_cnt is dead once the lists exist
             a.tw.part_cnt[4 * blockIdx.x] = (uint32_t)t0;
