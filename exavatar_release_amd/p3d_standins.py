@@ -8,7 +8,9 @@ non-synthetic configuration from running on MI355X at all.  The reference uses a
   mean squared distance to the 3 nearest other points) and ``module.py:543`` (K = 1: nearest template vertex);
 * ``SubdivideMeshes`` / ``Meshes`` -- ``smpl_x.py:73-100`` (two 4:1 subdivisions of the SMPL-X template, with vertex
   features carried along);
-* ``Meshes(...).verts_normals_packed()`` -- ``module.py:502``, ``smpl_x.py:140``, ``loss.py:156``;
+* ``Meshes(...).verts_normals_packed()`` -- ``module.py:502``, ``smpl_x.py:140``, ``loss.py:156`` (on a ROCm device its
+  ``index_add`` is not bit-reproducible: ``module.py:502`` takes ``exavatar_release_amd.vertex_normals`` instead,
+  INTEGRATION.md section 5);
 * ``matrix_to_rotation_6d`` / ``rotation_6d_to_matrix`` / ``matrix_to_quaternion`` / ``quaternion_to_matrix`` /
   ``axis_angle_to_matrix`` / ``matrix_to_axis_angle`` -- ``module.py:4,363-364,680``, ``smpl_x.py:12``;
 * ``look_at_view_transform`` -- the turntable cameras of the forward-only drivers of the renderer
@@ -143,7 +145,11 @@ class Meshes:
 
     def verts_normals_packed(self):
         """Area-weighted vertex normals (pytorch3d ``_compute_vertex_normals``): every face adds the cross product of
-        its two edges at each of its corners (= 2 * area * unit normal), the sums are normalised (eps 1e-6)."""
+        its two edges at each of its corners (= 2 * area * unit normal), the sums are normalised (eps 1e-6).
+        ``index_add`` adds with float atomics on a ROCm device, so there two calls on the same mesh can differ in the
+        last bits: device callers that need the same bits every time (``module.py:502``, the normals that feed
+        ``rgb_offset_net``) use ``exavatar_release_amd.vertex_normals``, which sums each vertex's faces in a fixed order
+        (INTEGRATION.md section 5).  On the CPU the sum is sequential and reproducible."""
         verts, faces = self.verts_packed(), self.faces_packed()
         vf = verts[faces]                                            # [F, 3, 3]
         n = torch.zeros_like(verts)
