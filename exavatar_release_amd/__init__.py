@@ -46,6 +46,11 @@ and for the forward kinematics that turn the pose into ``transform_mat_joint`` (
 ``batch_rigid_transform``, reference ``avatar/common/nets/module.py:389-411``, ``smplx/lbs.py:361-417``):
 
     from exavatar_release_amd import joint_transforms, batch_rigid_transform
+
+and for the SMPL-X template stage in front of them all (``get_neutral_pose_human(True, True)``, ``get_zero_pose_human()``
+and ``smpl_x.upsample_mesh``, reference ``avatar/common/nets/module.py:337-387``, ``avatar/common/utils/smpl_x.py:84-91``):
+
+    from exavatar_release_amd import BodyTemplate, MeshUpsampler
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -62,6 +67,7 @@ from .mlp import FusedMLP
 from .mesh_reg import LaplacianReg, mesh_laplacian_loss
 from .blend_shapes import BlendShapes, BlendTable, blend_offsets
 from .kinematics import batch_rigid_transform, joint_transforms
+from .body import BodyOutput, BodyTemplate, MeshUpsampler
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -69,4 +75,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
-           'blend_offsets', 'joint_transforms', 'batch_rigid_transform']
+           'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler']

@@ -125,6 +125,23 @@ class ExaMeshShading(ctypes.Structure):
                 ('background', ctypes.c_float * 3)]
 
 
+class ExaMeshUpsample(ctypes.Structure):
+    """The flat plan of one or two subdivision rounds (include/exa_mesh.h); the arrays are device pointers."""
+    _fields_ = [('levels', ctypes.c_int32), ('V0', ctypes.c_int32), ('V1', ctypes.c_int32), ('Vn', ctypes.c_int32),
+                ('par', c_void_p), ('off1', c_void_p), ('dep1', c_void_p), ('off2', c_void_p), ('dep2', c_void_p)]
+
+
+class ExaMeshBody(ctypes.Structure):
+    """The tables of the SMPL-X template stage (include/exa_mesh.h); `parents` and `up` are host pointers."""
+    _fields_ = [('V', ctypes.c_int32), ('L', ctypes.c_int32), ('J', ctypes.c_int32), ('nnz', ctypes.c_int32),
+                ('root', ctypes.c_int32), ('parents', ctypes.POINTER(ctypes.c_int32)),
+                ('v_base', c_void_p), ('dirs', c_void_p), ('pose_offsets', c_void_p),
+                ('jreg_off', c_void_p), ('jreg_col', c_void_p), ('jreg_val', c_void_p),
+                ('jregT_off', c_void_p), ('jregT_row', c_void_p), ('jregT_val', c_void_p),
+                ('weights', c_void_p), ('rot_pose', c_void_p), ('rot_inverse', c_void_p), ('rot_identity', c_void_p),
+                ('up', ctypes.POINTER(ExaMeshUpsample))]
+
+
 class ExaMlpNet(ctypes.Structure):
     """exa_mlp_net (include/exa_mlp.h): the arrays hold EXA_MLP_MAX_HEADS = 4 heads and EXA_MLP_MAX_LAYERS = 4 layers."""
     _fields_ = [('n_layers', ctypes.c_int32), ('in_width', ctypes.c_int32), ('shared_width', ctypes.c_int32),
@@ -171,6 +188,9 @@ _TP = ctypes.POINTER(ExaMeshTexture)
 _SHP = ctypes.POINTER(ExaMeshShading)
 _PP = ctypes.POINTER(c_void_p)       # host array of device pointers
 _IP = ctypes.POINTER(ctypes.c_int32)  # host array of int32
+_UP = ctypes.POINTER(ExaMeshUpsample)
+_BP = ctypes.POINTER(ExaMeshBody)
+_U64P = ctypes.POINTER(ctypes.c_uint64)
 
 # ---- the six ABIs
 # the Gaussian rasterizer with its image losses (exa_ssim_*, exa_photo_*, exa_l1_* report through exa_raster_last_error)
@@ -219,8 +239,8 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
             ExaRasterBackwardJob))
 
-# the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets and the forward
-# kinematics
+# the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets, the forward
+# kinematics, the mesh upsampling and the SMPL-X template stage
 MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -245,7 +265,15 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_kinematics_depths': (ctypes.c_int, [_I32, _IP, _IP]),
     'exa_mesh_kinematics_forward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 8),
     'exa_mesh_kinematics_backward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 11),
-},_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading))
+    # the mesh upsampling and the SMPL-X template stage (csrc/body.hip); the plan's arrays are host int32 arrays
+    'exa_mesh_upsample_plan': (ctypes.c_int, [_I32, _I32, _IP, _I32] + [_IP] * 7),
+    'exa_mesh_upsample_forward': (ctypes.c_int, [_UP, _I32, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_upsample_backward': (ctypes.c_int, [_UP, _I32, c_void_p, c_void_p, c_void_p, _U64, c_void_p, c_void_p]),
+    'exa_mesh_body_workspace_sizes': (ctypes.c_int, [_BP, _U64P, _U64P]),
+    'exa_mesh_body_forward': (ctypes.c_int, [_BP, c_void_p, c_void_p, c_void_p, _U64] + [c_void_p] * 6),
+    'exa_mesh_body_backward': (ctypes.c_int, [_BP, c_void_p, _U64] + [c_void_p] * 7 + [_U64, c_void_p, c_void_p,
+                                                                                       c_void_p]),
+}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody))
 
 # the K-nearest-neighbour search
 KNN = Abi('exa_knn', 'exa_knn.h', 100, {

@@ -51,6 +51,8 @@ SOURCES = {
     'blend_shapes.hip': ['-ffp-contract=off'],
     # the forward kinematics and their backward are defined operation by operation (include/exa_mesh.h)
     'kinematics.hip': ['-ffp-contract=off'],
+    # the mesh upsampling and the SMPL-X template stage are defined operation by operation (include/exa_mesh.h)
+    'body.hip': ['-ffp-contract=off'],
 }
 
 

@@ -23,6 +23,11 @@
  * And the forward kinematics that feed the skinning of that mesh: `exa_mesh_kinematics_*` are the reference's
  * `get_transform_mat_joint` (avatar/common/nets/module.py:389-411) under `exavatar_release_amd.kinematics`.
  *
+ * And the SMPL-X template stage in front of all of them: `exa_mesh_upsample_*` are the reference's `upsample_mesh`
+ * (avatar/common/utils/smpl_x.py:84-91, pytorch3d `SubdivideMeshes`) and `exa_mesh_body_*` its
+ * `get_neutral_pose_human(jaw_zero_pose=True, use_id_info=True)` + `get_zero_pose_human()`
+ * (avatar/common/nets/module.py:337-387), under `exavatar_release_amd.body`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -313,6 +318,143 @@ int exa_mesh_kinematics_backward(int32_t B, int32_t J, const int32_t* parents, c
                                  const float* joints, const float* pre, const float* grad_transforms,
                                  const float* grad_posed_joints, float* grad_pose, float* grad_rot, float* grad_joints,
                                  float* grad_pre, void* stream);
+
+/* ---- Mesh upsampling (reference upsample_mesh: pytorch3d SubdivideMeshes.subdivide_homogeneous, once or twice) -----
+ * One round appends, after the V vertices of a mesh, one vertex per unique edge, in ascending order of (low, high) (the
+ * edge's two vertex indices sorted); a face (v0, v1, v2) with the midpoints (m0 opposite v0: edge (v1, v2); m1: edge
+ * (v2, v0); m2: edge (v0, v1)) becomes (v0, m2, m1), (v1, m0, m2), (v2, m1, m0), (m0, m1, m2), the four groups of all
+ * faces concatenated in that order.  `levels` rounds (1 or 2) take V0 vertices to V1 = V0 + E0 and Vn = V1 + E1
+ * (Vn = V1 with one round).  The plan is flat:
+ *   par  [Vn - V0, 2] int32  the two parents (low, high) of fine vertex V0 + i: indices below V0 for i < V1 - V0 (a
+ *                            round-1 vertex), indices below V1 for the others (a round-2 vertex).
+ *   off1 [V0 + 1], dep1 [2 (V1 - V0)]  CSR: for every vertex p < V0 its dependants, the round-1 vertices d (V0 <= d <
+ *                            V1) that have p as a parent, ascending d (a vertex whose two parents are both p is
+ *                            listed twice).  off2 [V1 + 1], dep2 [2 (Vn - V1)]: the same for round 2 over p < V1 and
+ *                            V1 <= d < Vn.  The order is a function of the topology alone.
+ * Forward, one launch, x [V0, C] -> out [Vn, C] (1 <= C <= EXA_MESH_UP_MAX_CHANNELS), every operation rounded in fp32:
+ *   out[i] = x[i]                                 i < V0
+ *   out[i] = (val(a) + val(b)) * 0.5              (a, b) = par[i - V0];  val(p) = x[p] for p < V0, and for a round-1
+ *                                                 parent p the same expression over its own parents, recomputed in
+ *                                                 the thread (no second launch, no grid dependency)
+ * -- bit for bit what two `mean`s over two elements give.
+ * Backward, `levels` launches, no atomics.  With g [Vn, C]:
+ *   two rounds:  h[p] = g[p], then for d in p's round-2 dependants in order: h[p] = h[p] + g[d] * 0.5     (p < V1)
+ *   one round:   h = g
+ *   dx[v] = h[v]  (g_extra[v] + h[v] with a g_extra), then for d in v's round-1 dependants in order:
+ *           dx[v] = dx[v] + h[d] * 0.5                                                                      (v < V0)
+ * h is staged in the caller's workspace: V1 * C floats with two rounds, nothing with one.
+ * exa_mesh_upsample_plan is where every index is checked; the kernels still bound every offset and index they read from
+ * the plan (a parent outside its level gives NaN, a dependant or an offset outside its array is skipped), so no plan can
+ * make them read out of range. */
+#define EXA_MESH_UP_MAX_CHANNELS 8
+#define EXA_MESH_UP_MAX_VERTS (1 << 26)   /* Vn */
+
+typedef struct ExaMeshUpsample {
+    int32_t levels;                     /* 1 or 2 */
+    int32_t V0, V1, Vn;                 /* Vn == V1 with one round */
+    const int32_t* par;                 /* [dev] [Vn - V0, 2] */
+    const int32_t* off1;                /* [dev] [V0 + 1] */
+    const int32_t* dep1;                /* [dev] [2 (V1 - V0)] */
+    const int32_t* off2;                /* [dev] [V1 + 1]; unused with one round */
+    const int32_t* dep2;                /* [dev] [2 (Vn - V1)]; unused with one round */
+} ExaMeshUpsample;
+
+/* Host only: builds the plan of `levels` rounds over `faces` [F0, 3] (every index must lie in [0, V0):
+ * EXA_MESH_E_INVALID with a message naming the first that does not).  counts [3] receives V1, Vn and Fn = 4^levels F0.
+ * The output arrays are HOST memory, all given or all NULL (NULL: only the counts, to size them): par [Vn - V0, 2],
+ * faces_out [Fn, 3], off1 [V0 + 1], dep1 [2 (V1 - V0)], and with two rounds off2 [V1 + 1], dep2 [2 (Vn - V1)]. */
+int exa_mesh_upsample_plan(int32_t V0, int32_t F0, const int32_t* faces, int32_t levels, int32_t* counts, int32_t* par,
+                           int32_t* faces_out, int32_t* off1, int32_t* dep1, int32_t* off2, int32_t* dep2);
+
+/* One launch.  up HOST pointer (its arrays [dev]); x [dev] [V0, C]; out [dev] [Vn, C], fully written. */
+int exa_mesh_upsample_forward(const ExaMeshUpsample* up, int32_t C, const float* x, float* out, void* stream);
+
+/* `levels` launches.  g [dev] [Vn, C]; g_extra [dev] [V0, C] or NULL; ws [dev] of ws_bytes >= 4 V1 C with two rounds
+ * (NULL with one); dx [dev] [V0, C], fully written. */
+int exa_mesh_upsample_backward(const ExaMeshUpsample* up, int32_t C, const float* g, const float* g_extra, void* ws,
+                               uint64_t ws_bytes, float* dx, void* stream);
+
+/* ---- SMPL-X template stage (reference get_neutral_pose_human(True, True) + get_zero_pose_human) ---------------------
+ * What the reference computes with two `smplx_layer` forwards, a third `batch_rigid_transform` and two mesh
+ * subdivisions, as one stage.  Both poses are constants there (the big pose and its inverse; zero), so their rotations
+ * and pose-corrective offsets are data; what varies is coef [L] (shape, and expression if its directions are
+ * concatenated) and joint_offset [J, 3].  V vertices, 1 <= L <= EXA_MESH_BODY_MAX_COEF, 1 <= J <=
+ * EXA_MESH_KIN_MAX_JOINTS.  Every operation is rounded in fp32 and never contracted; every sum runs in an order that
+ * depends on the sizes and the tables alone.  With m = 3 v + c:
+ *   s = +0.0; for l = 0 .. L-1 in order: s = s + coef[l] * dirs[l][m];   v_shaped[m] = v_base[m] + s
+ *       (v_base = v_template + face_offset, added once by the caller; dirs is feature-major [L, 3 V])
+ *   v_posed[m] = v_shaped[m] + pose_offsets[m]                    (v_posed = v_shaped without pose_offsets)
+ *   Jr[j][c]: row j of the joint regressor travels compacted to its n_j non-zeros (jreg_off / jreg_col / jreg_val, a
+ *       CSR in ascending vertex order).  Lane t of 64 forms p_t = +0.0, then for i = t, t + 64, .. < n_j in order
+ *       p_t = p_t + val[i] * v_shaped[col[i]][c]; the 64 lanes are added as a tree, for off = 32, 16, 8, 4, 2, 1 in
+ *       order p_i = p_i + p_(i+off) for i < off; Jr[j][c] = p_0 + joint_offset[j][c] for j != root, p_0 for j == root.
+ *   chain A = exa_mesh_kinematics_forward(rot_in = rot_pose, joints = Jr): joint_neutral_pose (its posed joints), A
+ *   mesh = exa_skin_forward(points = v_posed, T = A, weights, no idx, trans = +0.0, no camera step)
+ *   mesh_upsampled = the upsampling above of mesh (C = 3)
+ *   chain B = exa_mesh_kinematics_forward(rot_in = rot_inverse, joints = joint_neutral_pose): transform_mat_neutral_pose
+ *   chain C = exa_mesh_kinematics_forward(rot_in = rot_identity, joints = Jr): joint_zero_pose (its posed joints)
+ * Seven launches.
+ *
+ * Backward, at most ten launches, no atomics.  Any of the five cotangents may be NULL (none); a step nothing reaches is
+ * not launched.
+ *   gB = grad_joints of exa_mesh_kinematics_backward(chain B; grad_transforms = g_transform_mat)
+ *   gm = the upsampling's backward (g = g_mesh_upsampled, g_extra = g_mesh);  gm = g_mesh without g_mesh_upsampled
+ *   exa_skin_backward(points = v_posed, grad_out = gm): grad_points = g_vp, grad_T = g_A
+ *   g_pA = g_joint_neutral_pose + gB (one of them alone where the other is missing)
+ *   gJA = grad_joints of exa_mesh_kinematics_backward(chain A; grad_transforms = g_A, grad_posed_joints = g_pA)
+ *   gJC = grad_joints of exa_mesh_kinematics_backward(chain C; grad_posed_joints = g_joint_zero_pose)
+ *   dJ[j][c] = gJA + gJC (one alone where the other is missing, +0.0 without both)
+ *   dL_djoint_offset[j] = dJ[j] for j != root, +0.0 for j == root
+ *   dvs[v][c] = g_vp[v][c] (+0.0 without gm), then for every non-zero (j, v) of the regressor in ascending j
+ *               (jregT_off / jregT_row / jregT_val, the transposed CSR): dvs = dvs + val * dJ[j][c]
+ *   dL_dcoef[l]: the 3 V elements m are cut into chunks of EXA_MESH_BODY_CHUNK = 256; in a chunk lane t owns element
+ *       m_t and forms q_t = dirs[l][m_t] * dvs[m_t] (+0.0 past 3 V); the 64 lanes of each of the four waves are added
+ *       by the tree above, the chunk's partial is ((w_0 + w_1) + w_2) + w_3, and
+ *       dL_dcoef[l] = +0.0, then for chunk = 0, 1, .. in order: dL_dcoef[l] = dL_dcoef[l] + partial[chunk][l].
+ * The forward's workspace holds what the backward reads (v_posed, Jr, A) and must stay untouched until then. */
+#define EXA_MESH_BODY_MAX_COEF 512
+#define EXA_MESH_BODY_CHUNK 256
+#define EXA_MESH_BODY_MAX_VERTS (1 << 24)   /* V */
+
+typedef struct ExaMeshBody {
+    int32_t V, L, J;                    /* vertices, coefficients, joints */
+    int32_t nnz;                        /* non-zeros of the joint regressor, 0 .. J V */
+    int32_t root;                       /* the joint whose joint_offset row is ignored, in [0, J) */
+    const int32_t* parents;             /* HOST [J]: the tree, as exa_mesh_kinematics_* take it */
+    const float* v_base;                /* [dev] [V, 3] */
+    const float* dirs;                  /* [dev] [L, 3 V] feature-major */
+    const float* pose_offsets;          /* [dev] [V, 3] or NULL */
+    const int32_t* jreg_off;            /* [dev] [J + 1] */
+    const int32_t* jreg_col;            /* [dev] [nnz] vertex of every non-zero, rows in order, ascending in a row */
+    const float* jreg_val;              /* [dev] [nnz] */
+    const int32_t* jregT_off;           /* [dev] [V + 1] */
+    const int32_t* jregT_row;           /* [dev] [nnz] joint of every non-zero, vertices in order, ascending in one */
+    const float* jregT_val;             /* [dev] [nnz] */
+    const float* weights;               /* [dev] [V, J] skinning weights */
+    const float* rot_pose;              /* [dev] [J, 3, 3] */
+    const float* rot_inverse;           /* [dev] [J, 3, 3] */
+    const float* rot_identity;          /* [dev] [J, 3, 3] identities */
+    const ExaMeshUpsample* up;          /* HOST pointer; up->V0 == V */
+} ExaMeshBody;
+
+/* Host only: the bytes of the forward's and the backward's workspace, from V, L, J and up's counts alone. */
+int exa_mesh_body_workspace_sizes(const ExaMeshBody* body, uint64_t* fwd_bytes, uint64_t* bwd_bytes);
+
+/* body HOST pointer; coef [dev] [L]; joint_offset [dev] [J, 3]; fwd_ws [dev] of fwd_ws_bytes >= fwd_bytes.  Outputs,
+ * each [dev], required, fully written: mesh_upsampled [Vn, 3], mesh [V, 3], joint_neutral_pose [J, 3],
+ * transform_mat_neutral_pose [J, 4, 4], joint_zero_pose [J, 3]. */
+int exa_mesh_body_forward(const ExaMeshBody* body, const float* coef, const float* joint_offset, void* fwd_ws,
+                          uint64_t fwd_ws_bytes, float* mesh_upsampled, float* mesh, float* joint_neutral_pose,
+                          float* transform_mat_neutral_pose, float* joint_zero_pose, void* stream);
+
+/* fwd_ws, joint_neutral_pose: the forward's.  g_* [dev], shaped as the outputs, each may be NULL.  bwd_ws [dev] of
+ * bwd_ws_bytes >= bwd_bytes.  dL_dcoef [dev] [L] and dL_djoint_offset [dev] [J, 3]: each may be NULL (not wanted: the
+ * steps only it needs are not launched), fully written when given. */
+int exa_mesh_body_backward(const ExaMeshBody* body, const void* fwd_ws, uint64_t fwd_ws_bytes,
+                           const float* joint_neutral_pose, const float* g_mesh_upsampled, const float* g_mesh,
+                           const float* g_joint_neutral_pose, const float* g_transform_mat_neutral_pose,
+                           const float* g_joint_zero_pose, void* bwd_ws, uint64_t bwd_ws_bytes, float* dL_dcoef,
+                           float* dL_djoint_offset, void* stream);
 
 #ifdef __cplusplus
 }
