@@ -62,7 +62,7 @@ def _compose_launch(cjobs, store_ctx, device, capturing, sorted_event=None):
             a.host_header, a.header_tag = dev_addr, tag
             c.report = (slot, tag)
         elif capturing and rz._capture_report_c is not None and k < len(rz._capture_report_c) and rz._capture_report_c[k] is not None:
-            a.host_header = rz._hdr_pool.dev_base + 16 * rz._capture_report_c[k][0]
+            a.host_header = rz._hdr_pool.addr(rz._capture_report_c[k][0])
             a.header_tag = rz._capture_report_c[k][1]
     if sorted_event is None:
         _lib.check(lib.exa_raster_forward_compose_batch(arr, K, int(store_ctx), ctypes.c_void_p(stream_obj.cuda_stream)))

@@ -52,7 +52,6 @@ no autograd history in this mode (the loss is the only differentiable output).  
 the replay itself; an iteration that overflowed restores them from the copy the graph makes first and runs again.
 """
 import ctypes
-import time
 import warnings
 
 import torch
@@ -60,7 +59,7 @@ import torch
 from . import _lib
 
 from . import rasterizer as rz
-from .renderer import ITERATION_RENDERS, _sh_degree, camera_block_device, render_iteration
+from .renderer import ITERATION_RENDERS, _TrustedFocal, _sh_degree, render_iteration
 
 _ASSET_KEYS = ('mean_3d', 'scale', 'rotation', 'opacity')
 _IMG_ONLY = (True, False, False) * 5
@@ -168,7 +167,7 @@ class GraphedIteration:
         self._ptr_table = torch.zeros(16, dtype=torch.int64, device=device)
         self._cap = None
         self._caps_hint = None if capacities is None else [int(c) for c in capacities]   # capacities of the next capture
-        self._intr, self._focal_src, self._focal_ver = None, None, None
+        self._focal = _TrustedFocal()
         self._bg_src, self._bg_ver = None, None
         self._last_needs = None         # (P_scene, P_human, needs of the three plain renders) of the last checked iteration
         self._reports_checked = True
@@ -185,10 +184,7 @@ class GraphedIteration:
         # and node storage with it): wait for the device first.  Re-captures and close() are rare (a change of P, an
         # overflow, the end of training), the wait costs them nothing.
         torch.cuda.synchronize(self.device)
-        if rz._hdr_pool is not None:
-            for s in (cap.slots or []) + (getattr(cap, 'slots_c', None) or []):
-                if s is not None:
-                    rz._hdr_pool.release(s[0])
+        self._drop_slots(cap)
         # Let go of the recordings and their static tensors NOW (not whenever the cyclic collector finds the old capture): their
         # memory then goes back to this object's graph pool and the next recording re-uses it.  A pool of its own per capture
         # made every change of P pay ~90 ms of hipFree for the previous capture's segments (tools/gpu_capture_cost.py).
@@ -198,6 +194,11 @@ class GraphedIteration:
                 setattr(cap, name, None)
             except AttributeError:
                 pass
+
+    @staticmethod
+    def _drop_slots(cap):
+        if rz._hdr_pool is not None:
+            rz._hdr_pool.release_reports(cap.slots + cap.slots_c)
 
     def close(self):
         """Release the captured graphs, their static tensors and the reserved report slots (after waiting for the device).
@@ -223,10 +224,7 @@ class GraphedIteration:
                     # would invalidate that capture.  Give the report slots back and let the graphs go with the object; the
                     # replays they belong to were queued before the capture began.
                     cap, self._cap = self._cap, None
-                    if rz._hdr_pool is not None:
-                        for s in (cap.slots or []) + (getattr(cap, 'slots_c', None) or []):
-                            if s is not None:
-                                rz._hdr_pool.release(s[0])
+                    self._drop_slots(cap)
                 else:
                     self.close()
         except Exception:  # noqa: BLE001 -- interpreter shutdown
@@ -337,8 +335,7 @@ class GraphedIteration:
                         for _ in range(n_jobs + len(cap.slots_c)):
                             taken.append(pool.reserve()[:2])
                     except Exception:
-                        for slot, _tag in taken:
-                            pool.release(slot)
+                        pool.release_reports(taken)
                         raise
                     cap.slots, cap.slots_c = taken[:n_jobs], taken[n_jobs:]
                 if self._pool is None:
@@ -454,97 +451,34 @@ class GraphedIteration:
             else:
                 torch._foreach_copy_(cap.in_raw, [s_.detach() for s_ in src])
 
-    def _camera(self, cam_param):
-        """Write the camera block; returns (tan, check) with check = None or (pool, slot, tag) to poll after the replay."""
-        cap_cam = self._cam
-        f = cam_param['focal']
-        pool = rz._pool()
-        trusted = self._intr is not None and f is self._focal_src and getattr(f, '_version', None) == self._focal_ver
-        flag = chk = None
-        if self._intr is not None and not trusted and pool is not None:
-            fslot, ftag, faddr = pool.take()
-            flag, chk = (faddr, ftag), (pool, fslot, ftag)
-        intr, checking = camera_block_device(cam_param, self.shape, cap_cam, self._intr if flag else None, flag)
-        if not checking:
-            self._intr, self._focal_src, self._focal_ver = intr, f, getattr(f, '_version', None)
-            chk = None
-        return (intr[0], intr[1]), chk
-
-    def _focal_ok(self, chk, f):
-        pool, fslot, ftag = chk
-        w, b = pool.words, 4 * fslot
-        t_end = time.perf_counter() + 5e-3
-        while w[b + 3] != ftag and time.perf_counter() < t_end:
-            pass
-        if w[b + 3] != ftag:
-            torch.cuda.current_stream(self.device).synchronize()
-        if w[b + 3] != ftag or w[b] != 1:
-            self._intr = None
-            return False
-        self._focal_src, self._focal_ver = f, getattr(f, '_version', None)
-        return True
-
     def _reset_reports(self, cap):
         if rz._hdr_pool is not None:
-            w = rz._hdr_pool.words
-            for s in cap.slots + cap.slots_c:
-                if s is not None:
-                    w[4 * s[0] + 3] = 0
+            rz._hdr_pool.clear_reports(cap.slots + cap.slots_c)
 
     def _overflowed(self, cap):
         """Wait for the header reports of the last forward replay; returns None or the capacities the renders need."""
         if not self.check or self._reports_checked:
             return None
         self._reports_checked = True
-        w = rz._hdr_pool.words if rz._hdr_pool is not None else None
-        needs, over = [], False
-        for k, s in enumerate(cap.slots):
-            if s is None or w is None:
-                torch.cuda.current_stream(self.device).synchronize()
-                need, ovf = self._device_header(cap, k)
-            else:
-                b = 4 * s[0]
-                t_end = time.perf_counter() + 5e-3
-                while w[b + 3] != s[1] and time.perf_counter() < t_end:
-                    pass
-                if w[b + 3] != s[1]:
-                    torch.cuda.current_stream(self.device).synchronize()
-                if w[b + 3] == s[1]:
-                    need, ovf = int(w[b]), int(w[b + 1])
-                else:
-                    need, ovf = self._device_header(cap, k)
-            needs.append(need)
-            over = over or bool(ovf)
+        got = None if None in cap.slots else rz._hdr_pool.collect(cap.slots, 5e-3, device=self.device)
+        if got is None:
+            raise RuntimeError('exavatar_release_amd: GraphedIteration needs pinned host memory mapped for the device '
+                               '(header reports); use the eager render_iteration on this system')
+        needs = [need for need, _ in got]
         n3 = needs if self.merge else [needs[0], needs[1], needs[3]]
         self._last_needs = (cap.sizes[0] // 3, cap.sizes[5] // 3, n3)
-        return needs if over else None
+        return needs if any(ovf for _, ovf in got) else None
 
     def _slot_needs(self, cap, patience=2.5e-4):
         """``num_rendered`` of every plain and composite render of the last forward replay, from their reports; None when one has
         not landed or reports are unavailable.  Waits at most ``patience`` seconds: the composites report ~0.15 ms into the forward
         graph, and a caller that reaches its backward sooner (no loss kernels in between) loses nothing by spinning that long --
         the backward graph could not start before the forward graph is through anyway."""
-        if rz._hdr_pool is None:
+        pool, slots = rz._hdr_pool, cap.slots + cap.slots_c
+        got = None if pool is None or None in slots else pool.collect(slots, patience, shared=True)
+        if got is None or any(ovf for _, ovf in got):
             return None
-        w = rz._hdr_pool.words
-        slots = cap.slots + cap.slots_c
-        if any(s is None for s in slots):
-            return None
-        t_end = None
-        for s in slots:
-            i = 4 * s[0] + 3
-            while w[i] != s[1]:
-                if t_end is None:
-                    t_end = time.perf_counter() + patience
-                elif time.perf_counter() > t_end:
-                    return None
-        if any(w[4 * s[0] + 1] != 0 for s in slots):
-            return None
-        return [int(w[4 * s[0]]) for s in slots]
-
-    def _device_header(self, cap, k):
-        raise RuntimeError('exavatar_release_amd: GraphedIteration needs pinned host memory mapped for the device '
-                           '(header reports); use the eager render_iteration on this system')
+        return [need for need, _ in got]
 
     def _replay_forward(self, assets, cam_param, bg, dens, refill, loss_args=()):
         """(Re-)capture if needed, fill the static inputs, replay the forward graph.  Returns the capture."""
@@ -557,7 +491,7 @@ class GraphedIteration:
         for _ in range(4):
             cap = self._cap
             # camera first: tan(fov) is part of the capture key
-            tan, chk = self._camera(cam_param)
+            tan, checking = self._focal.before(cam_param, self.shape, self._cam)
             if self._bg_src is not bg or self._bg_ver != getattr(bg, '_version', None):
                 with torch.no_grad():
                     torch.mul(torch.as_tensor(bg, dtype=torch.float32, device=dev).reshape(-1), 1.0, out=self._cam[35:38])
@@ -578,7 +512,7 @@ class GraphedIteration:
             cap.fwd.replay()
             self._serial += 1
             self._reports_checked = False
-            if chk is not None and not self._focal_ok(chk, cam_param['focal']):
+            if checking and not self._focal.after(dev):
                 # the focal length changed: derive the intrinsics again, maybe re-capture.  The replay that just ran used the
                 # stale intrinsics; with the loss in the graph its backward has already updated the densification
                 # statistics -- put them back (as _grow does for an overflowed replay) before the iteration runs again

@@ -194,11 +194,14 @@ class _HdrPool:
         self.tag = tag + 1 if tag < 0x7ffffff0 else 1
         return tag
 
+    def addr(self, slot):
+        return self.dev_base + 16 * slot
+
     def take(self):
         """(slot, tag, device address) of the next ring slot."""
         i = self.next
         self.next = (i + 1) % self.N
-        return i, self._next_tag(), self.dev_base + 16 * i
+        return i, self._next_tag(), self.addr(i)
 
     def reserve(self):
         """(slot, tag, device address) of a slot outside the ring, held until :meth:`release`."""
@@ -206,12 +209,66 @@ class _HdrPool:
             raise RuntimeError('exavatar_release_amd: all %d reserved header-report slots are taken: too many live '
                                'GraphedRenderer / GraphedIteration objects (close() the ones no longer used)' % self.RESERVED)
         i = self.free_reserved.pop()
-        self.words[4 * i + 3] = 0
-        return i, self._next_tag(), self.dev_base + 16 * i
+        self.clear(i)
+        return i, self._next_tag(), self.addr(i)
 
     def release(self, slot):
         if slot >= self.N and slot not in self.free_reserved:
             self.free_reserved.append(slot)
+
+    def release_reports(self, reports):
+        """Give back the reserved slots of ``(slot, tag)`` reports; None entries, ring slots and free slots are skipped."""
+        for r in reports:
+            if r is not None:
+                self.release(r[0])
+
+    def clear(self, slot):
+        """Zero the tag word (before a replay rewrites the slot: the old report must not be taken for the new one)."""
+        self.words[4 * slot + 3] = 0
+
+    def clear_reports(self, reports):
+        w = self.words
+        for r in reports:
+            if r is not None:
+                w[4 * r[0] + 3] = 0
+
+    def landed(self, slot, tag):
+        """Whether the report with ``tag`` is in the slot; never waits."""
+        return self.words[4 * slot + 3] == tag
+
+    def read(self, slot):
+        """Words 0 and 1 of the slot: ``(needed, overflow)`` of a render, ``(flag, _)`` of a focal-length check."""
+        w, b = self.words, 4 * slot
+        return w[b], w[b + 1]                 # (a c_uint32 array hands out Python ints)
+
+    def wait(self, slot, tag, spin_s, stream=None, t_end=None, device=None):
+        """Whether the report with ``tag`` landed: the host spins on the word (no runtime call) until ``t_end`` (default: for
+        ``spin_s`` seconds from now); a ``stream`` (or ``device``: its current stream, looked up only now) that is still
+        behind then is waited for and the word tested once more."""
+        w, i = self.words, 4 * slot + 3
+        if w[i] == tag:
+            return True
+        if t_end is None:
+            t_end = time.perf_counter() + spin_s
+        while w[i] != tag and time.perf_counter() < t_end:
+            pass
+        if w[i] != tag and (stream is not None or device is not None):
+            (stream if stream is not None else torch.cuda.current_stream(device)).synchronize()
+        return w[i] == tag
+
+    def collect(self, reports, spin_s, device=None, shared=False):
+        """``read`` of every ``(slot, tag)`` report, or None if one did not land.  Each report is waited for as by :meth:`wait`
+        (``spin_s``, then ``device``); ``shared``: ONE budget of ``spin_s`` for all, starting at the first that has not landed."""
+        w, got, t_end = self.words, [], None
+        for slot, tag in reports:
+            b = 4 * slot
+            if w[b + 3] != tag:
+                if shared and t_end is None:
+                    t_end = time.perf_counter() + spin_s
+                if not self.wait(slot, tag, spin_s, t_end=t_end, device=device):
+                    return None
+            got.append((w[b], w[b + 1]))
+        return got
 
 
 _hdr_pool = None
@@ -232,27 +289,18 @@ def _pool():
 
 def _await_report(slot, tag, stream):
     """(needed capacity, overflow flag) of the report with ``tag`` in pool slot ``slot``.  The scatter stage writes it
-    ~35 us into the forward: the host spins on the word (no runtime call); a stream that is far behind is waited for."""
-    w, i = _hdr_pool.words, 4 * slot + 3
-    if w[i] != tag:
-        t_end = time.perf_counter() + 2e-3
-        while w[i] != tag and time.perf_counter() < t_end:
-            pass
-        if w[i] != tag:
-            stream.synchronize()
-            if w[i] != tag:
-                raise RuntimeError('exavatar_release_amd: the header report of a render never arrived')
-    return int(w[i - 3]), int(w[i - 2])
+    ~35 us into the forward: the host spins on the word for 2 ms; a stream that is far behind is waited for."""
+    if not _hdr_pool.wait(slot, tag, 2e-3, stream):
+        raise RuntimeError('exavatar_release_amd: the header report of a render never arrived')
+    return _hdr_pool.read(slot)
 
 
 def _landed_need(report):
     """``num_rendered`` of a ``(slot, tag)`` report that has landed and did not overflow, else None; never waits."""
-    if report is None or _hdr_pool is None:
+    if report is None or _hdr_pool is None or not _hdr_pool.landed(report[0], report[1]):
         return None
-    w, b = _hdr_pool.words, 4 * report[0]
-    if w[b + 3] != report[1] or w[b + 1] != 0:
-        return None
-    return int(w[b])
+    need, overflow = _hdr_pool.read(report[0])
+    return None if overflow else need
 
 
 def _record_overflow(key, need, cap, how):
@@ -395,7 +443,7 @@ def _fill_forward_job(a, j, report=None):
     a.out_color, a.out_depth, a.out_alpha = _plane_ptrs(j.planes, j.H, j.W)
     a.keep_sorted_keys = 1 if j.keep_keys else 0
     if report is not None:           # (slot, tag) of a pool slot
-        a.host_header, a.header_tag = _hdr_pool.dev_base + 16 * report[0], report[1]
+        a.host_header, a.header_tag = _hdr_pool.addr(report[0]), report[1]
     else:
         a.host_header, a.header_tag = None, 0
 
@@ -770,8 +818,7 @@ def _compiled_node():
             if pool is None:
                 raise RuntimeError('pinned host memory cannot be mapped for the device')
             _lib.load()
-            _exa_torch.init(_lib.LIB_PATH, pool.buf.data_ptr() + 16 * pool.compiled_first, pool.dev_base + 16 * pool.compiled_first,
-                            pool.COMPILED)
+            _exa_torch.init(_lib.LIB_PATH, pool.buf[pool.compiled_first:].data_ptr(), pool.addr(pool.compiled_first), pool.COMPILED)
             _compiled = _exa_torch
         except Exception as e:  # noqa: BLE001
             if config.compiled_node == 'require':

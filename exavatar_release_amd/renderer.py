@@ -9,7 +9,6 @@ hard-coded ``.cuda()``, the default background is created per call (the referenc
 from one read-back of the camera tensors (same formulas, see ``forward``).
 """
 import ctypes
-import time
 import warnings
 
 import torch
@@ -113,6 +112,42 @@ def camera_block_device(cam_param, img_shape, out38, expect=None, flag=None):
         f.data_ptr() if check else None, intr[3], intr[4], flag[0] if check else None, flag[1] if check else 0,
         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return intr, check
+
+
+class _TrustedFocal:
+    """The intrinsics record of the last verified frame and the focal tensor it was verified for (the graphed classes).  A
+    focal tensor that is the very object (and version) of the last verified frame is trusted; a new object (a data loader
+    hands out a fresh tensor per frame) is compared ON THE DEVICE with the remembered focal length by the camera kernel,
+    which reports into a pinned host word polled after the replay: no read-back."""
+
+    def __init__(self):
+        self.intr, self.src, self.ver, self._pending = None, None, None, None
+
+    def before(self, cam_param, img_shape, out38):
+        """Write the camera block into ``out38``; returns ``(tan, pending)``: ask :meth:`after` once the frame is queued."""
+        from . import rasterizer as rz
+        f = cam_param['focal']
+        pool = rz._pool()
+        trusted = self.intr is not None and f is self.src and getattr(f, '_version', None) == self.ver
+        flag = None
+        if self.intr is not None and not trusted and pool is not None:
+            slot, tag, addr = pool.take()
+            flag = (addr, tag)
+        intr, checking = camera_block_device(cam_param, img_shape, out38, self.intr if flag else None, flag)
+        if checking:
+            self._pending = (pool, slot, tag, f)
+        else:                                 # intrinsics came from the host path (memo or read-back): verified
+            self.intr, self.src, self.ver, self._pending = intr, f, getattr(f, '_version', None), None
+        return (intr[0], intr[1]), checking
+
+    def after(self, device):
+        """Whether the pending check found the focal length unchanged; if not, the next :meth:`before` reads it back."""
+        (pool, slot, tag, f), self._pending = self._pending, None
+        if pool.wait(slot, tag, 5e-3, device=device) and pool.read(slot)[0] == 1:
+            self.src, self.ver = f, getattr(f, '_version', None)
+            return True
+        self.intr = None
+        return False
 
 
 _probe_cache = []      # most recent first: (P, device, zeros [P, 3]); treat the probes as read-only
@@ -405,20 +440,23 @@ class GraphedRenderer:
         self._last = {}                                       # key -> (source tensor, its version) of the previous frame
         self._slot = None                                     # (slot, tag) of the header report baked into the graph
         self._bg_src, self._bg_ver = None, None
-        self._intr, self._focal_src, self._focal_ver = None, None, None     # last verified intrinsics record / focal tensor
+        self._focal = _TrustedFocal()
         self.captures = 0
 
     def close(self):
         """Release the captured graph, its static outputs and the reserved report slot (after waiting for the device: a graph
         must not be destroyed while one of its replays is still executing).  The object captures anew when called again."""
-        from . import rasterizer as rz
         if self._graph is not None and not torch.cuda.is_current_stream_capturing():
             # (garbage-collected in the middle of somebody else's stream capture: a device wait is illegal there and would
             #  invalidate that capture; the replays of this graph were queued before the capture began)
             torch.cuda.synchronize(self.device)
         self._graph, self._outs, self._tile, self._tan = None, None, None, None
-        if self._slot is not None and rz._hdr_pool is not None:
-            rz._hdr_pool.release(self._slot[0])
+        self._drop_slot()
+
+    def _drop_slot(self):
+        from . import rasterizer as rz
+        if rz._hdr_pool is not None:
+            rz._hdr_pool.release_reports([self._slot])
         self._slot = None
 
     def __enter__(self):
@@ -478,10 +516,8 @@ class GraphedRenderer:
                 # the captured call reports its header into ONE pinned host slot (a plain store from the scatter kernel,
                 # include/exa_raster.h: host_header): every replay rewrites it, the host resets the tag before a replay and
                 # polls it afterwards -- no read-back, no synchronisation per frame
+                self._drop_slot()                             # the graph that wrote into it is gone
                 pool = rz._pool()
-                if self._slot is not None and pool is not None:
-                    pool.release(self._slot[0])               # the graph that wrote into it is gone
-                self._slot = None
                 got = pool.reserve() if pool is not None else None   # outside the ring eager renders draw from
                 if got is not None:
                     self._slot = (got[0], got[1])
@@ -526,49 +562,21 @@ class GraphedRenderer:
             if self._bg_src is not bg or self._bg_ver != getattr(bg, '_version', None):
                 self._cam[35:38].copy_(torch.as_tensor(bg, dtype=torch.float32).reshape(-1))
                 self._bg_src, self._bg_ver = bg, getattr(bg, '_version', None)
-        f = cam_param['focal']
         with rz._on_device(dev):
             for _ in range(4):
-                # A focal tensor that is the very object (and version) of the last verified frame is trusted; a new object
-                # (a data loader hands out a fresh tensor per frame) is compared ON THE DEVICE with the remembered focal
-                # length by the camera kernel, which reports into a pinned host word polled after the replay: no read-back.
-                pool = rz._pool()
-                trusted = self._intr is not None and f is self._focal_src and getattr(f, '_version', None) == self._focal_ver
-                flag = None
-                if self._intr is not None and not trusted and pool is not None:
-                    fslot, ftag, faddr = pool.take()
-                    flag = (faddr, ftag)
-                intr, checking = camera_block_device(cam_param, self.shape, self._cam, self._intr if flag else None, flag)
-                if not checking:                              # intrinsics came from the host path (memo or read-back): verified
-                    self._intr, self._focal_src, self._focal_ver = intr, f, getattr(f, '_version', None)
-                tan = (intr[0], intr[1])
+                tan, checking = self._focal.before(cam_param, self.shape, self._cam)
                 if self._graph is None or self._tan != tan:
                     self._capture(tan)
-                if self._slot is not None:
-                    words, b = rz._hdr_pool.words, 4 * self._slot[0]
-                    words[b + 3] = 0                          # (the previous replay's report has been read: no store in flight)
+                pool, slot = rz._hdr_pool, self._slot
+                if slot is not None:
+                    pool.clear(slot[0])                       # (the previous replay's report has been read: no store in flight)
                 self._graph.replay()
-                if checking:
-                    words_f, bf = pool.words, 4 * fslot
-                    t_end = time.perf_counter() + 5e-3
-                    while words_f[bf + 3] != ftag and time.perf_counter() < t_end:
-                        pass
-                    if words_f[bf + 3] != ftag:
-                        torch.cuda.current_stream(dev).synchronize()
-                    if words_f[bf + 3] != ftag or words_f[bf] != 1:
-                        self._intr = None                     # the focal length changed: derive it again (one read-back),
-                        continue                              # re-capture if tan(fov) moved, and render this frame again
-                    self._focal_src, self._focal_ver = f, getattr(f, '_version', None)
+                if checking and not self._focal.after(dev):
+                    continue                                  # the focal length changed: re-capture if tan(fov) moved, render again
                 if not self.check:
                     break
-                if self._slot is not None:
-                    t_end = time.perf_counter() + 5e-3
-                    while words[b + 3] != self._slot[1] and time.perf_counter() < t_end:
-                        pass
-                    if words[b + 3] != self._slot[1]:
-                        torch.cuda.current_stream(dev).synchronize()
-                if self._slot is not None and words[b + 3] == self._slot[1]:
-                    need, overflow = int(words[b]), int(words[b + 1])
+                if slot is not None and pool.wait(slot[0], slot[1], 5e-3, device=dev):
+                    need, overflow = pool.read(slot[0])
                 else:
                     need, overflow = rz.read_header(self._tile)[:2]
                 if not overflow:

@@ -4,6 +4,8 @@ for bit -- images, radii, every gradient incl. ``mean_2d.grad`` and the fused de
 cameras and values per iteration, a change of P (densify / prune, reference avatar/main/config.py:17-20), a forced
 instance-buffer overflow, a new focal length, depth / mask gradients and ``no_grad`` calls.  The eager path itself is held
 against the oracle in tests/test_gpu_parity.py.  /root/reference is never read here."""
+import gc
+
 import pytest
 import torch
 
@@ -382,3 +384,32 @@ def test_a_change_of_sh_degree_with_constant_shapes_recaptures(dev):
             if deg == 0:
                 _same(res[0][:5], res[1][:5], 'sh degree 0 images (call %d)' % n)
         assert it.captures == 3                    # one per degree
+
+
+def test_closing_graphed_objects_gives_every_reserved_report_slot_back(dev):
+    """A ``GraphedRenderer`` holds one reserved header-report slot, a merging ``GraphedIteration`` five (three plain renders,
+    two composites): ``close()`` hands all of them back exactly once, and closing again changes nothing."""
+    h, w = 160, 192
+    sets = _sets(4000, 1500, 111, dev)
+    cam = {k: t.to(dev) for k, t in scenes.ring_camera(h, w, 2, 40, radius=3.2, center=(0.0, 0.0, 3.0), focal=F).items()}
+    bg = torch.full((3,), 0.5, device=dev)
+    pool = exa.rasterizer._pool()
+    assert pool is not None
+    gc.collect()                               # (objects earlier tests left to the collector give their slots back now, not below)
+    n0 = len(pool.free_reserved)
+    gr = exa.GraphedRenderer(4000, (h, w), dev)
+    it = exa.GraphedIteration((h, w), dev, merge=True)
+    out = gr(sets[0], cam, bg)
+    assert out['img'].shape == (3, h, w) and bool(torch.isfinite(out['img']).all())
+    s, hu, r = _leaves(sets)
+    res = it(s, hu, r, cam, bg)
+    sum(res[n]['img'].sum() for n in exa.ITERATION_RENDERS).backward()
+    torch.cuda.synchronize()
+    assert s['mean_3d'].grad is not None and bool(torch.isfinite(s['mean_3d'].grad).all())
+    assert len(pool.free_reserved) == n0 - 6
+    gr.close()
+    it.close()
+    assert len(pool.free_reserved) == n0 and len(set(pool.free_reserved)) == n0
+    gr.close()
+    it.close()
+    assert len(pool.free_reserved) == n0 and len(set(pool.free_reserved)) == n0

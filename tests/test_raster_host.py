@@ -156,3 +156,180 @@ def test_capacity_for_states_the_policy_once(policy):
     # a shape nobody measured: 0 = measure it (exact mode)
     del rz._seen_D[key]
     assert rz._capacity_for(key, 0) == 0
+
+
+# ---- header-report pool: slot arithmetic, waiting and release over plain host memory ---------------------------------
+DEV_BASE = 0x7f0000001000
+RING, TOTAL = 8, 12                  # ring slots 0..7, reserved slots 8..11
+
+
+@pytest.fixture
+def pool():
+    p = object.__new__(rz._HdrPool)
+    p.words = (ctypes.c_uint32 * (4 * TOTAL))(*range(100, 100 + 4 * TOTAL))
+    p.dev_base, p.N, p.next, p.tag, p.free_reserved = DEV_BASE, RING, 0, 1, [11, 10]
+    return p
+
+
+class _Stream:
+    """Stands in for a stream: counts ``synchronize()`` calls; ``lands`` = (pool, slot, tag) the wait makes arrive."""
+
+    def __init__(self, lands=None):
+        self.calls, self.lands = 0, lands
+
+    def synchronize(self):
+        self.calls += 1
+        if self.lands is not None:
+            p, slot, tag = self.lands
+            p.words[4 * slot + 3] = tag
+
+
+@pytest.mark.parametrize('slot', [0, 5, 9])          # first slot, a ring slot, a reserved slot
+def test_pool_slot_operations_touch_the_right_words_only(pool, slot):
+    before = list(pool.words)
+    assert pool.addr(slot) == DEV_BASE + 16 * slot
+    assert pool.read(slot) == (before[4 * slot], before[4 * slot + 1])
+    assert type(pool.read(slot)[0]) is int and type(pool.read(slot)[1]) is int
+    assert pool.landed(slot, before[4 * slot + 3]) and not pool.landed(slot, before[4 * slot + 3] + 1)
+    assert list(pool.words) == before                # addr / read / landed write nothing
+    pool.clear(slot)
+    after = list(pool.words)
+    assert after[4 * slot + 3] == 0 and not pool.landed(slot, before[4 * slot + 3]) and pool.landed(slot, 0)
+    after[4 * slot + 3] = before[4 * slot + 3]
+    assert after == before                           # every other word, the neighbouring slots' included, is untouched
+    pool.words[4 * slot], pool.words[4 * slot + 1] = 77, 1
+    assert pool.read(slot) == (77, 1)
+
+
+def test_pool_take_and_reserve_hand_out_addr(pool):
+    assert pool.take() == (0, 1, DEV_BASE) and pool.take() == (1, 2, DEV_BASE + 16)
+    assert pool.reserve() == (10, 3, DEV_BASE + 160) and pool.words[43] == 0 and pool.free_reserved == [11]
+
+
+def test_pool_wait_returns_a_landed_report_without_the_clock(pool, monkeypatch):
+    def clock():
+        raise AssertionError('the clock was consulted')
+    monkeypatch.setattr(rz.time, 'perf_counter', clock)
+    pool.words[4 * 9 + 3] = 41
+    s = _Stream()
+    assert pool.wait(9, 41, 1e-3, s) is True and s.calls == 0
+    assert pool.collect([(9, 41)], 1e-3) == [(136, 137)] and pool.collect([(9, 41)], 1e-3, shared=True) == [(136, 137)]
+
+
+def test_pool_wait_falls_back_on_the_stream_once(pool):
+    import time
+    s = _Stream(lands=(pool, 5, 41))
+    t0 = time.perf_counter()
+    assert pool.wait(5, 41, 1e-3, s) is True
+    assert time.perf_counter() - t0 >= 1e-3 and s.calls == 1
+    # a stream that does not bring the report: False, after spin_s and not before, one synchronize
+    s = _Stream()
+    t0 = time.perf_counter()
+    assert pool.wait(5, 42, 1e-3, s) is False
+    assert time.perf_counter() - t0 >= 1e-3 and s.calls == 1
+    # no stream: nothing to synchronise
+    t0 = time.perf_counter()
+    assert pool.wait(5, 42, 1e-3) is False
+    assert time.perf_counter() - t0 >= 1e-3
+
+
+def test_pool_wait_with_a_deadline_in_the_past_returns_at_once(pool, monkeypatch):
+    import time
+    t_end = time.perf_counter() - 1.0
+    polls = []
+    real = time.perf_counter
+    monkeypatch.setattr(rz.time, 'perf_counter', lambda: polls.append(1) or real())
+    s = _Stream()
+    assert pool.wait(5, 42, 10.0, s, t_end=t_end) is False and s.calls == 1
+    assert len(polls) == 1                           # one look at the clock: the loop body never ran
+    assert pool.wait(5, 42, 10.0, _Stream(lands=(pool, 5, 42)), t_end=t_end) is True
+
+
+def test_pool_collect_reads_every_report_or_none(pool, monkeypatch):
+    import time
+    stream = _Stream()
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda device=None: stream)
+    reports = [(8, 7), (9, 8), (10, 9)]
+    pool.words[4 * 8 + 3] = 7
+    # one shared budget, starting at the first report that has not landed (9; 10 never gets a budget of its own); no stream wait
+    t0 = time.perf_counter()
+    assert pool.collect(reports, 1e-3, shared=True) is None
+    assert 1e-3 <= time.perf_counter() - t0 < 0.5 and stream.calls == 0
+    # a budget per report, then the device's current stream, then give up at the first that is missing
+    t0 = time.perf_counter()
+    assert pool.collect(reports, 1e-3, device=torch.device('cpu')) is None
+    assert time.perf_counter() - t0 >= 1e-3 and stream.calls == 1
+    stream.lands = (pool, 9, 8)                      # the stream wait brings report 9; 10 has landed
+    pool.words[4 * 10 + 3] = 9
+    assert pool.collect(reports, 1e-3, device=torch.device('cpu')) == [(132, 133), (136, 137), (140, 141)] and stream.calls == 2
+    assert pool.collect(reports, 1e-3, shared=True) == [(132, 133), (136, 137), (140, 141)]
+    assert pool.collect([], 1e-3) == []
+
+
+def test_pool_release_reports_skips_none_ring_and_free_slots(pool):
+    assert pool.reserve()[0] == 10 and pool.free_reserved == [11]
+    pool.release_reports([None, (3, 5), (10, 6), None, (10, 6), (11, 9)])
+    assert sorted(pool.free_reserved) == [10, 11]
+    pool.release(10)
+    pool.release(2)
+    assert sorted(pool.free_reserved) == [10, 11]
+
+
+# ---- the trusted focal tensor of the graphed classes -------------------------------------------------------------
+@pytest.fixture
+def focal(pool, monkeypatch):
+    """A ``_TrustedFocal`` over the fake pool; ``camera_block_device`` is replaced by a recorder that checks on the
+    'device' exactly when the real one would for a float32 focal tensor (``expect`` and ``flag`` given)."""
+    from exavatar_release_amd import renderer
+    calls = []
+
+    def block(cam_param, img_shape, out38, expect=None, flag=None):
+        calls.append((expect, flag))
+        check = expect is not None and flag is not None
+        return (expect if check else (0.5, 0.4, None, 170.0, 170.0)), check
+    monkeypatch.setattr(renderer, 'camera_block_device', block)
+    monkeypatch.setattr(rz, '_hdr_pool', pool)
+    stream = _Stream()
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda device=None: stream)
+    return renderer._TrustedFocal(), calls, stream
+
+
+def test_trusted_focal_protocol(pool, focal):
+    tf, calls, stream = focal
+    f = torch.tensor([170.0, 170.0])
+    out38 = torch.zeros(38)
+    # first frame: host path, verified at once, no slot
+    assert tf.before({'focal': f}, (8, 8), out38) == ((0.5, 0.4), False)
+    assert calls[-1] == (None, None) and pool.next == 0 and tf.src is f and tf.ver == f._version
+    # same object and version: trusted, no slot taken, no device check
+    assert tf.before({'focal': f}, (8, 8), out38) == ((0.5, 0.4), False)
+    assert calls[-1] == (None, None) and pool.next == 0
+    # a new object: a ring slot is taken, the check is pending
+    g = f.clone()
+    pool.words[3] = 0
+    assert tf.before({'focal': g}, (8, 8), out38) == ((0.5, 0.4), True)
+    assert pool.next == 1 and calls[-1] == (tf.intr, (DEV_BASE, 1)) and tf.src is f
+    pool.words[0], pool.words[3] = 1, 1              # the kernel reports "unchanged" with tag 1
+    assert tf.after(torch.device('cpu')) is True and tf.src is g and tf.ver == g._version and tf.intr is not None
+    assert stream.calls == 0
+    # the same object written in place: a new version is checked again; flag word 0 = changed: intrinsics forgotten
+    g.add_(1.0)
+    assert tf.before({'focal': g}, (8, 8), out38)[1] is True and pool.next == 2
+    pool.words[4], pool.words[7] = 0, 2
+    assert tf.after(torch.device('cpu')) is False and tf.intr is None
+    # ... so the next frame goes the host path again and is verified
+    assert tf.before({'focal': g}, (8, 8), out38)[1] is False and calls[-1] == (None, None) and tf.src is g and pool.next == 2
+    # a report that never lands (after the spin and one stream wait): forgotten as well
+    h = g.clone()
+    pool.words[11] = 0
+    assert tf.before({'focal': h}, (8, 8), out38)[1] is True and pool.next == 3
+    assert tf.after(torch.device('cpu')) is False and tf.intr is None and stream.calls == 1 and tf.src is g
+
+
+def test_pool_clear_reports_zeroes_the_tags_of_its_reports_only(pool):
+    before = list(pool.words)
+    pool.clear_reports([(9, 1), None, (0, 2)])
+    after = list(pool.words)
+    assert after[3] == 0 and after[39] == 0
+    after[3], after[39] = before[3], before[39]
+    assert after == before
