@@ -51,6 +51,12 @@ and for the SMPL-X template stage in front of them all (``get_neutral_pose_human
 and ``smpl_x.upsample_mesh``, reference ``avatar/common/nets/module.py:337-387``, ``avatar/common/utils/smpl_x.py:84-91``):
 
     from exavatar_release_amd import BodyTemplate, MeshUpsampler
+
+and for the arm and hand regularisers of the loss block (``ArmRGBReg``, ``HandRGBReg``, ``HandMeanReg`` and ``smpl_x.get_arm``,
+reference ``avatar/common/nets/loss.py:148-197``, ``avatar/common/utils/smpl_x.py:139-148``, called at
+``avatar/main/model.py:223,249-251``):
+
+    from exavatar_release_amd import ArmRGBReg, HandRGBReg, HandMeanReg, get_arm
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -68,6 +74,7 @@ from .mesh_reg import LaplacianReg, mesh_laplacian_loss
 from .blend_shapes import BlendShapes, BlendTable, blend_offsets
 from .kinematics import batch_rigid_transform, joint_transforms
 from .body import BodyOutput, BodyTemplate, MeshUpsampler
+from .vertex_regs import ArmPlan, ArmRGBReg, HandMeanReg, HandRGBReg, arm_neighbors, arm_rgb_loss, get_arm
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -75,4 +82,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'SSIM', 'RGBLoss', 'PhotometricLoss', 'MeshRenderer', 'get_face_index_map_xy', 'Fragments',
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
-           'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler']
+           'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
+           'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm']

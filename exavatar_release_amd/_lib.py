@@ -273,6 +273,15 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_body_forward': (ctypes.c_int, [_BP, c_void_p, c_void_p, c_void_p, _U64] + [c_void_p] * 6),
     'exa_mesh_body_backward': (ctypes.c_int, [_BP, c_void_p, _U64] + [c_void_p] * 7 + [_U64, c_void_p, c_void_p,
                                                                                        c_void_p]),
+    # the arm and hand regularisers (csrc/vertex_regs.hip)
+    'exa_mesh_arm_plan': (ctypes.c_int, [_I32, _I32, _I32, ctypes.c_float] + [c_void_p] * 11),
+    'exa_mesh_arm_loss_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 7),
+    'exa_mesh_arm_loss_backward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 5),
+    'exa_mesh_hand_rgb_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_mesh_hand_rgb_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 4 + [_U64] + [c_void_p] * 3),
+    'exa_mesh_hand_rgb_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 7),
+    'exa_mesh_hand_mean_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 5),
+    'exa_mesh_hand_mean_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 6),
 }, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody))
 
 # the K-nearest-neighbour search
@@ -367,6 +376,10 @@ def knn_workspace_size(N, P1, P2, K):
 
 def laplacian_workspace_size(B, V, C):
     return size_query(MESH, 'exa_mesh_laplacian_workspace_size', B, V, C)
+
+
+def hand_rgb_workspace_size(B, N):
+    return size_query(MESH, 'exa_mesh_hand_rgb_workspace_size', B, N)
 
 
 def blend_workspace_size(K, N):

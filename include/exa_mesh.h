@@ -28,6 +28,10 @@
  * `get_neutral_pose_human(jaw_zero_pose=True, use_id_info=True)` + `get_zero_pose_human()`
  * (avatar/common/nets/module.py:337-387), under `exavatar_release_amd.body`.
  *
+ * And the arm and hand regularisers of that mesh: `exa_mesh_arm_*` and `exa_mesh_hand_*` are the reference's
+ * `ArmRGBReg`, `HandRGBReg` and `HandMeanReg` (avatar/common/nets/loss.py:148-197), under
+ * `exavatar_release_amd.vertex_regs`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -455,6 +459,101 @@ int exa_mesh_body_backward(const ExaMeshBody* body, const void* fwd_ws, uint64_t
                            const float* g_joint_neutral_pose, const float* g_transform_mat_neutral_pose,
                            const float* g_joint_zero_pose, void* bwd_ws, uint64_t bwd_ws_bytes, float* dL_dcoef,
                            float* dL_djoint_offset, void* stream);
+
+/* ---- Arm and hand regularisers (reference ArmRGBReg, HandRGBReg, HandMeanReg, loss.py:148-197) -----------------------
+ * Three more per-vertex losses of the upsampled mesh, V vertices, B batch elements, three channels.  Every operation
+ * is rounded in fp32 and never contracted; every sum runs in the order stated here.  No atomics, no memset: every
+ * output element is written by the launch that owns it.  Masks are bytes (0 = out, anything else = in).
+ *
+ * ARM.  is_upper / is_lower [V] select U upper-arm and L lower-arm vertices.  For a lower vertex l and an upper vertex u
+ *   dx = x_l - x_u, dy = y_l - y_u, dz = z_l - z_u;   the pair is VALID iff |dx| < dist_x_thr  (a float32 comparison)
+ *   d2 = (dx * dx + dy * dy) + dz * dz;   key(l, u) = (bits(d2), u), ordered by bits(d2), then by the vertex index u.
+ *       bits(d2) is the IEEE pattern of d2 as an unsigned integer -- d2 >= +0, so that is its numeric order -- and
+ *       0x7fc00000 for a NaN, which therefore sorts after +inf.  No square root is taken: it is monotone, so it can
+ *       only merge neighbouring keys into ties; the reference's 9999 sentinel of an invalid pair never wins, because
+ *       k <= n_min.
+ *   n_l = number of valid u;   n_min = min over the lower vertices of n_l (0 when L == 0);   k = min(K_max, n_min)
+ *   target[b,l,c] = t / (float)k  where  t = +0.0, then for the k smallest keys of l in ascending order:
+ *                   t = t + rgb[b, u, c].    k == 0 gives 0 / 0 = NaN, the reference's mean over an empty set; it
+ *                   is not trapped.
+ *   d = rgb[b,l,c] - target;   loss[b,l,c] = d * d;   every vertex outside the lower list: loss = d = +0.0
+ *   backward: dL_drgb[b,l,c] = (2 * d) * grad_loss[b,l,c];  +0.0 for every vertex outside the lower list.  The target
+ *   is detached and the mesh gets no gradient (in the reference it reaches only the indices).
+ * The lists are in ascending vertex order; the result does not depend on that, the key carries the index.
+ *
+ * HAND RGB.  Two lists r_idx, l_idx [N] (the right and the left hand's vertices, ascending) and their inverse ranks
+ * r_rank, l_rank [V] (position in the list, -1 outside).
+ *   mean_r[b,c]: the list is cut into chunks of EXA_MESH_REG_CHUNK = 256 rows; partial[chunk] = +0.0, then for the
+ *       chunk's rows i in list order partial = partial + rgb[b, r_idx[i], c];  s = +0.0, then for chunk = 0, 1, .. in
+ *       order s = s + partial[chunk];  mean_r = s / (float)N.   mean_l the same over l_idx.
+ *   loss[b,i,c] = dr * dr + dl * dl,   dr = rgb[b, r_idx[i], c] - mean_r[b,c],  dl = rgb[b, l_idx[i], c] - mean_l[b,c]
+ *   backward (the means are detached), per vertex v through the ranks, ir = r_rank[v], il = l_rank[v]:
+ *       tr = grad_loss[b,ir,c] * (2 * (rgb[b,v,c] - mean_r[b,c]));   tl = grad_loss[b,il,c] * (2 * (rgb[b,v,c] - mean_l[b,c]))
+ *       dL_drgb[b,v,c] = tr + tl in both lists, tr or tl alone in one, +0.0 in neither.
+ *
+ * HAND MEAN.  h_idx [H] (the union of the hands, ascending) and its inverse ranks h_rank [V]; normal [V, 3].  With
+ * o = offset[b,v,:], n = normal[v,:], v = h_idx[j]:
+ *   norm = sqrt((o0 * o0 + o1 * o1) + o2 * o2);   s = norm < 1e-12f ? 1e-12f : norm;   q_c = o_c / s
+ *   dot = (n0 * q0 + n1 * q1) + n2 * q2;   loss[b,j] = dot < 0 ? +0.0 : dot      (a NaN stays a NaN in both selects)
+ *   backward, torch's for normalize and clamp: g = dot >= 0 ? grad_loss[b,j] : 0 (the gradient passes at equality);
+ *       dq_c = g * n_c;   a_c = dq_c / s;
+ *       norm >= 1e-12f:  t = (dq0 * (q0 / s) + dq1 * (q1 / s)) + dq2 * (q2 / s);  w = (-t) / norm;
+ *                        dL_doffset[b,v,c] = a_c + o_c * w
+ *       otherwise:       dL_doffset[b,v,c] = a_c        (a zero row gets g * n_c / 1e-12f, which is finite)
+ *       +0.0 for every vertex outside the list.  normal gets no gradient.
+ * A list entry outside [0, V) reads nothing and contributes NaN.  B == 0 or an empty list is a successful no-op where
+ * nothing is left to write. */
+#define EXA_MESH_ARM_MAX_K 64           /* K_max: one key per lane of a wave */
+#define EXA_MESH_ARM_WAVES 8            /* lower vertices per workgroup of the selection */
+#define EXA_MESH_ARM_TILE 1024          /* upper records staged in LDS at a time */
+#define EXA_MESH_ARM_HEADER_INTS 4      /* header: U, L, k, n_min */
+#define EXA_MESH_REG_CHUNK 256
+
+/* The neighbour plan of one mesh: three launches (compaction by one workgroup; selection, one wave per lower vertex,
+ * the grid sized by `rows`; the reduction of the counts to k).  mesh [dev] [V, 3]; is_upper, is_lower [dev] [V] bytes;
+ * rows = the caller's bound on L, 0 .. V (V is always safe): a lower vertex of rank >= rows is not selected for and
+ * gets NaN in the loss, and n_min runs over the first min(L, rows) lower vertices.  1 <= K_max <= 64; dist_x_thr finite
+ * and > 0.  Outputs, all [dev]: upper_rec, lower_rec [V, 4] fp32 records {x, y, z, index bits} (16-byte aligned, the
+ * first U and L written); lower_rank [V] int32, fully written; nbr [rows, K_max] int32 (row r < L: the indices of its
+ * K_max smallest keys in ascending key order, -1 where it has fewer); n_valid [rows] (n_l, rows < L); wg_min
+ * [ceil(rows / EXA_MESH_ARM_WAVES)] scratch; header [EXA_MESH_ARM_HEADER_INTS] int32 {U, L, k, n_min}, fully written.
+ * Nothing is read back: U, L and k stay on the device. */
+int exa_mesh_arm_plan(int32_t V, int32_t rows, int32_t K_max, float dist_x_thr, const float* mesh,
+                      const uint8_t* is_upper, const uint8_t* is_lower, float* upper_rec, float* lower_rec,
+                      int32_t* lower_rank, int32_t* nbr, int32_t* n_valid, int32_t* wg_min, int32_t* header,
+                      void* stream);
+
+/* One launch.  rgb [dev] [B, V, 3]; lower_rank, nbr, header: the plan's (rows, K_max as there); loss, d [dev] [B, V, 3],
+ * fully written (d is what the backward reads). */
+int exa_mesh_arm_loss_forward(int32_t B, int32_t V, int32_t rows, int32_t K_max, const float* rgb,
+                              const int32_t* lower_rank, const int32_t* nbr, const int32_t* header, float* loss, float* d,
+                              void* stream);
+
+/* One launch.  d [dev] the forward's; grad_loss [dev] [B, V, 3]; dL_drgb [dev] [B, V, 3], fully written. */
+int exa_mesh_arm_loss_backward(int32_t B, int32_t V, const float* d, const float* grad_loss, const int32_t* lower_rank,
+                               float* dL_drgb, void* stream);
+
+/* Bytes of the hand-rgb forward's workspace (the chunk partials). */
+int exa_mesh_hand_rgb_workspace_size(int32_t B, int32_t N, uint64_t* out_bytes);
+
+/* Two launches.  rgb [dev] [B, V, 3]; r_idx, l_idx [dev] [N]; ws [dev] of ws_bytes >= the size above; means [dev]
+ * [B, 2, 3] (right, left; what the backward reads) and loss [dev] [B, N, 3], fully written. */
+int exa_mesh_hand_rgb_forward(int32_t B, int32_t V, int32_t N, const float* rgb, const int32_t* r_idx,
+                              const int32_t* l_idx, void* ws, uint64_t ws_bytes, float* means, float* loss, void* stream);
+
+/* One launch.  means [dev] the forward's; grad_loss [dev] [B, N, 3]; r_rank, l_rank [dev] [V]; dL_drgb [dev]
+ * [B, V, 3], fully written. */
+int exa_mesh_hand_rgb_backward(int32_t B, int32_t V, int32_t N, const float* rgb, const float* means,
+                               const float* grad_loss, const int32_t* r_rank, const int32_t* l_rank, float* dL_drgb,
+                               void* stream);
+
+/* One launch.  offset [dev] [B, V, 3]; normal [dev] [V, 3]; h_idx [dev] [H]; loss [dev] [B, H], fully written. */
+int exa_mesh_hand_mean_forward(int32_t B, int32_t V, int32_t H, const float* offset, const float* normal,
+                               const int32_t* h_idx, float* loss, void* stream);
+
+/* One launch.  grad_loss [dev] [B, H]; h_rank [dev] [V]; dL_doffset [dev] [B, V, 3], fully written. */
+int exa_mesh_hand_mean_backward(int32_t B, int32_t V, int32_t H, const float* offset, const float* normal,
+                                const float* grad_loss, const int32_t* h_rank, float* dL_doffset, void* stream);
 
 #ifdef __cplusplus
 }
