@@ -1,6 +1,6 @@
 """What every feature module needs to hand torch tensors to the C ABIs: data pointers, the current stream, workspaces
-from the torch allocator, the launch of a stream-taking call, incoming gradients, the argument checks the features share
-and the package's run-time ``config``."""
+from the torch allocator, the launch of a stream-taking call, the warm-up before a stream capture, incoming gradients, the
+argument checks the features share and the package's run-time ``config``."""
 import ctypes
 
 import torch
@@ -78,6 +78,16 @@ def _on_device(device):
     """``torch.cuda.device(device)`` only when it is not the current device already (the context manager costs ~10 us
     per entry, twice per render, in an eager training loop)."""
     return _NO_CTX if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+
+
+def warm_up(device, fn):
+    """The warm-up ``torch.cuda.graph`` asks for before a capture: ``fn()`` on a fresh side stream, joined at both ends; a device wait."""
+    side, main = torch.cuda.Stream(device=device), torch.cuda.current_stream(device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        fn()
+    main.wait_stream(side)
+    torch.cuda.synchronize(device)
 
 
 def launch(abi, name, device, *args):

@@ -61,9 +61,9 @@ def _compose_launch(cjobs, store_ctx, device, capturing, sorted_event=None):
             slot, tag, dev_addr = pool.take()
             a.host_header, a.header_tag = dev_addr, tag
             c.report = (slot, tag)
-        elif capturing and rz._capture_report_c is not None and k < len(rz._capture_report_c) and rz._capture_report_c[k] is not None:
-            a.host_header = rz._hdr_pool.addr(rz._capture_report_c[k][0])
-            a.header_tag = rz._capture_report_c[k][1]
+        elif capturing and rz.report_for(k, True) is not None:
+            slot, tag = rz.report_for(k, True)
+            a.host_header, a.header_tag = rz._hdr_pool.addr(slot), tag
     if sorted_event is None:
         _lib.check(lib.exa_raster_forward_compose_batch(arr, K, int(store_ctx), ctypes.c_void_p(stream_obj.cuda_stream)))
         return
@@ -184,10 +184,8 @@ class _Compose(torch.autograd.Function):
                 a.compose_geom_a, a.compose_P_a, a.compose_capacity_b = ja.geom_ptr, ja.P, jb.capacity
                 # the composite's packed lists fill a fraction of its buffer (sized for both sources): its own report, written
                 # by the first kernel of its forward, says how many batch slots the backward has to visit
-                need_c = rz._landed_need(c.report)
-                a.used_slots = (need_c + 63) // 64 if need_c else 0
-                if rz._capture_used is not None and k < len(rz._capture_used[1]):
-                    a.used_slots = int(rz._capture_used[1][k])
+                need_c, used = rz._landed_need(c.report), rz.used_for(k, True)
+                a.used_slots = int(used) if used is not None else (need_c + 63) // 64 if need_c else 0
                 me = (id(ctx), k)
                 if ctx.fold and (jb.stash is None or jb.stash[0] == me):
                     # leave them with B's job: B's own backward runs after this one (the token orders it) and adds its

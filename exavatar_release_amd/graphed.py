@@ -57,8 +57,8 @@ import warnings
 import torch
 
 from . import _lib
-
 from . import rasterizer as rz
+from ._device import warm_up
 from .renderer import ITERATION_RENDERS, _TrustedFocal, _sh_degree, render_iteration
 
 _ASSET_KEYS = ('mean_3d', 'scale', 'rotation', 'opacity')
@@ -278,12 +278,10 @@ class GraphedIteration:
         cap.dens = None if dens is None else [t for t in dens if t is not None]
         cap.loss_args = [t.detach().clone() for t in loss_args]          # static: the recorded loss reads these
         self._fill_inputs(cap, assets)
-        saved = (rz.config.mode, rz.config.fixed_capacity, rz.config.on_overflow)
         # (the eager renders below run with capacities that may be estimates: an overflow there is repaired in place whatever the
         #  user's policy says -- the captured graph has its own overflow path, _grow)
-        rz.config.on_overflow = 'retry'
         try:
-            with torch.enable_grad():
+            with rz.capture_scope(on_overflow='retry') as scope, torch.enable_grad():
                 # Capacities of the three plain renders (scene, human, refined human).  After an overflow: what the reports
                 # asked for.  After a change of P (densify / prune): the last measured needs scaled by the change -- a
                 # re-capture then costs two recordings, no eager pass, and an estimate that turns out too small is caught
@@ -309,9 +307,7 @@ class GraphedIteration:
                 rz.config.mode, rz.config.fixed_capacity = 'capacity', list(caps)
                 if self.captures == 0:
                     # once per object: a warm-up on a side stream (as torch.cuda.graph asks for), forward + backward
-                    side = torch.cuda.Stream(device=dev)
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side):
+                    def iteration():
                         res = self._render(cap, None)
                         if self.loss_fn is not None:
                             torch.autograd.grad(self.loss_fn(res, *cap.loss_args), cap.in_list, allow_unused=True)
@@ -319,25 +315,16 @@ class GraphedIteration:
                             torch.autograd.grad([res[k]['img'] for k in ITERATION_RENDERS], cap.in_list,
                                                 grad_outputs=[torch.ones_like(res[k]['img']) for k in ITERATION_RENDERS],
                                                 allow_unused=True)
-                        del res
-                    torch.cuda.current_stream(dev).wait_stream(side)
-                    torch.cuda.synchronize(dev)
+                    warm_up(dev, iteration)
                 # header reports of the plain renders go to reserved pinned-host slots (outside the ring eager calls use)
                 pool = rz._pool()
-                n_jobs = 3 if self.merge else 5
                 # (the composites report too -- {slots in use, overflow}, written by the first kernel of their forward: their backward
                 #  visits only the batch slots in use, ExaRasterBackwardJob.used_slots, _backward below)
-                cap.slots = [None] * n_jobs
-                cap.slots_c = [None, None] if self.merge else []
-                if pool is not None:
-                    taken = []
-                    try:                # reserve() raises when the reserved region is exhausted: give back what this capture took
-                        for _ in range(n_jobs + len(cap.slots_c)):
-                            taken.append(pool.reserve()[:2])
-                    except Exception:
-                        pool.release_reports(taken)
-                        raise
-                    cap.slots, cap.slots_c = taken[:n_jobs], taken[n_jobs:]
+                cap.slots, cap.slots_c = [None] * (3 if self.merge else 5), [None, None] if self.merge else []
+                if pool is not None:    # (reserve() raises when the reserved region is exhausted: the handler below gives back
+                    for lst in (cap.slots, cap.slots_c):                                     # what this capture took)
+                        for i in range(len(lst)):
+                            lst[i] = pool.reserve()[:2]
                 if self._pool is None:
                     # a pool lives as long as a graph recorded into it: this one-kernel recording keeps it (and the memory
                     # earlier captures gave back to it) across re-captures
@@ -348,28 +335,24 @@ class GraphedIteration:
                     self._keeper = (keeper, k_t)
                 cap.pool = self._pool
                 cap.fwd = torch.cuda.CUDAGraph()
-                rz._capture_report = cap.slots
-                rz._capture_report_c = cap.slots_c
                 if self.loss_fn is not None:
                     cap.flat = torch.zeros(sum(cap.sizes), **f32)
                     if cap.dens:
                         cap.dens_backup = [torch.empty_like(t) for t in cap.dens]
-                try:
-                    with torch.cuda.graph(cap.fwd, pool=cap.pool):
-                        if cap.dens_backup:
-                            # the replay's backward updates the statistics; an overflowed replay is thrown away and must
-                            # leave them as they were (_grow restores them from here)
-                            torch._foreach_copy_(cap.dens_backup, cap.dens)
-                        res = self._render(cap, dens)
-                        if self.loss_fn is not None:
-                            loss = self.loss_fn(res, *cap.loss_args)
-                            if not (torch.is_tensor(loss) and loss.numel() == 1 and loss.requires_grad):
-                                raise ValueError('GraphedIteration: loss_fn must return a scalar tensor that depends on the renders')
-                            grads = torch.autograd.grad(loss, cap.in_list + cap.probes, allow_unused=True)
-                            cap.unused = self._pack(grads, cap, cap.flat)
-                            cap.loss = loss.detach()
-                finally:
-                    rz._capture_report = rz._capture_report_c = None
+                scope.report, scope.report_c = cap.slots, cap.slots_c
+                with torch.cuda.graph(cap.fwd, pool=cap.pool):
+                    if cap.dens_backup:
+                        # the replay's backward updates the statistics; an overflowed replay is thrown away and must
+                        # leave them as they were (_grow restores them from here)
+                        torch._foreach_copy_(cap.dens_backup, cap.dens)
+                    res = self._render(cap, dens)
+                    if self.loss_fn is not None:
+                        loss = self.loss_fn(res, *cap.loss_args)
+                        if not (torch.is_tensor(loss) and loss.numel() == 1 and loss.requires_grad):
+                            raise ValueError('GraphedIteration: loss_fn must return a scalar tensor that depends on the renders')
+                        grads = torch.autograd.grad(loss, cap.in_list + cap.probes, allow_unused=True)
+                        cap.unused = self._pack(grads, cap, cap.flat)
+                        cap.loss = loss.detach()
                 cap.outs = res
                 cap.out_list = [res[k][n] for k in ITERATION_RENDERS for n in ('img', 'depthmap', 'mask')]
                 # radius / is_vis of the five renders: static tensors the replay rewrites (the composites' are written by their
@@ -377,8 +360,9 @@ class GraphedIteration:
                 cap.radii = {k: (res[k]['radius'], res[k]['is_vis']) for k in ITERATION_RENDERS}
                 cap.bwd = {}
                 self.captures += 1
-        finally:
-            rz.config.mode, rz.config.fixed_capacity, rz.config.on_overflow = saved
+        except BaseException:
+            self._drop_slots(cap)           # (nobody else will: the capture never became self._cap)
+            raise
         # the backward graph of the usual case -- gradients for the five colour images only -- is
         # recorded right away; other patterns (depth / mask gradients, fewer images) on first use
         if self.loss_fn is None and not self.tight_backward:
@@ -391,30 +375,20 @@ class GraphedIteration:
     def _capture_backward(self, cap, pattern, used=None):
         """Backward graph for the set of outputs that receive a gradient (``pattern``: 15 booleans).  ``used``: None, or the
         batch slots in use per plain job and per composite job, baked into the launches (the TIGHT graph, see _backward)."""
-        dev = self.device
-        f32 = dict(dtype=torch.float32, device=dev)
         g_in = [torch.zeros_like(o) if on else None for o, on in zip(cap.out_list, pattern)]
         outs = [o for o, on in zip(cap.out_list, pattern) if on]
         gos = [g for g in g_in if g is not None]
         inputs = cap.in_list + cap.probes
-        saved = (rz.config.mode, rz.config.fixed_capacity)
-        try:
-            rz.config.mode, rz.config.fixed_capacity = 'capacity', list(cap.caps)
-            base = self._ptr_table.data_ptr()
-            rz._capture_grad_ind = {g_in[3 * i].data_ptr(): base + 8 * i for i in range(5) if g_in[3 * i] is not None}
-            rz._capture_used = used
-            with torch.enable_grad():
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=cap.pool):
-                    grads = torch.autograd.grad(outs, inputs, grad_outputs=gos, allow_unused=True, retain_graph=True)
-                # The gradients stay where the recording left them (static tensors of the graph's pool); _backward gathers
-                # them into a fresh private buffer with ONE concatenation kernel after the replay -- packing inside the graph
-                # AND cloning the packed buffer afterwards moved the 14 MB twice.
-                unused = [gr is None for gr in grads]
-                flat = [None if gr is None else gr.reshape(-1) for gr in grads]
-        finally:
-            rz.config.mode, rz.config.fixed_capacity = saved
-            rz._capture_grad_ind = rz._capture_used = None
+        grad_ind = {g_in[3 * i].data_ptr(): self._ptr_table.data_ptr() + 8 * i for i in range(5) if g_in[3 * i] is not None}
+        with rz.capture_scope(used=used, grad_ind=grad_ind, mode='capacity', fixed_capacity=list(cap.caps)), torch.enable_grad():
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=cap.pool):
+                grads = torch.autograd.grad(outs, inputs, grad_outputs=gos, allow_unused=True, retain_graph=True)
+            # The gradients stay where the recording left them (static tensors of the graph's pool); _backward gathers
+            # them into a fresh private buffer with ONE concatenation kernel after the replay -- packing inside the graph
+            # AND cloning the packed buffer afterwards moved the 14 MB twice.
+            unused = [gr is None for gr in grads]
+            flat = [None if gr is None else gr.reshape(-1) for gr in grads]
         self.backward_captures += 1
         if used is None:
             cap.bwd[pattern] = (g, g_in, flat, unused)

@@ -44,9 +44,11 @@ for a few microseconds per call and were removed in round 5.)  Under stream capt
 polled: the report goes to a reserved slot the owner of the graph reads after each replay
 (``GraphedRenderer`` / ``GraphedIteration``), or the caller checks ``read_header`` itself.
 """
+import contextlib
 import ctypes
 import threading
 import time
+import types
 import warnings
 import weakref
 from typing import NamedTuple
@@ -76,16 +78,11 @@ class GaussianRasterizationSettings(NamedTuple):
 _debug_last = {}  # only filled when config.keep_debug (tools/): workspaces of the most recent forward
 _seen_D = {}      # (device index, P, H, W) -> largest instance capacity a call of that shape needed
 overflow_events = []   # (key, needed, capacity, 'retried' | 'raised') of every overflow seen (bounded; for tests / logs)
-_capture_report = None   # [(slot, tag) | None per job]: reserved header-report slots baked into the batched call being
-#                          CAPTURED (set by GraphedRenderer / GraphedIteration around their capture)
 _overlap = {}             # device index -> (side stream, event recorded when the sources' sorted lists are complete): set by a
 #                           captured keep_keys batch, consumed by the composite call that follows it (config.overlap_composites)
-_capture_report_c = None  # the same for the composite jobs of the call being captured (GraphedIteration)
-_capture_used = None      # (used batch slots per plain job, per composite job) baked into the backward being RECORDED
-#                           (ExaRasterBackwardJob.used_slots; GraphedIteration checks them against every replay's reports)
-_capture_grad_ind = None  # {data_ptr of a static dL/dcolor buffer: device address of its pointer-table entry}: set by
-#                           GraphedIteration while it RECORDS a backward graph (ExaRasterBackwardJob.dL_dcolor_indirect)
-_last_handles = None     # host job records of the most recent keep_keys call (handed to rasterize_gaussians_batch's caller)
+_capture = None           # the fields of the active capture_scope (below), None outside one.  A process-wide attribute ON
+#                           PURPOSE, not threading.local / contextvars: both backwards read it while torch.autograd.grad runs
+#                           inside a capture, on autograd's own device thread, not on the thread that entered the scope
 _tls = threading.local()  # .is_vis: the `radii > 0` tensors the per-Gaussian kernel of the most recent call of this thread wrote
 #                           (ExaRasterForwardJob.is_vis), picked up by the renderer's output dict via take_is_vis()
 
@@ -97,6 +94,47 @@ def take_is_vis():
     v = getattr(_tls, 'is_vis', None)
     _tls.is_vis = None
     return v
+
+
+@contextlib.contextmanager
+def capture_scope(report=None, report_c=None, used=None, grad_ind=None, jobs=None, **overrides):
+    """The ONE way GraphedRenderer / GraphedIteration tell the calls they record what to bake in.  Installs ``_capture`` (yielded;
+    its fields may be assigned in the body) and assigns the ``config`` attributes in ``overrides`` (the body may assign more):
+    however the body ends, ``_capture`` is None again and ``config`` is what it was on entry.  While a scope is active single
+    renders take the Python node.  ``report`` / ``report_c``: per plain / composite job ``(slot, tag)`` of the reserved
+    header-report slot of the call being CAPTURED (read by the owner of the graph after each replay), or None.  ``used``: None or
+    (per plain job, per composite job) batch slots in use, for the backward being RECORDED (ExaRasterBackwardJob.used_slots).
+    ``grad_ind``: None or {data_ptr of a static dL/dcolor buffer: device address of its pointer-table entry}
+    (ExaRasterBackwardJob.dL_dcolor_indirect).  ``jobs``: None or a list every ``_Rasterize.forward`` appends its jobs to."""
+    global _capture
+    if _capture is not None:
+        raise RuntimeError('exavatar_release_amd: a capture scope is already active (scopes do not nest)')
+    entry = dict(vars(config))
+    _capture = types.SimpleNamespace(report=report, report_c=report_c, used=used, grad_ind=grad_ind, jobs=jobs)
+    try:
+        vars(config).update(overrides)
+        yield _capture
+    finally:
+        _capture, config.__dict__ = None, entry
+
+
+def _nth(seq, k):
+    return seq[k] if seq is not None and k < len(seq) else None
+
+
+def report_for(k, composite=False):
+    """``(slot, tag)`` the active scope holds for plain (composite) job ``k``; None where there is none, no scope included."""
+    return _nth(_capture.report_c if composite else _capture.report, k) if _capture is not None else None
+
+
+def used_for(k, composite=False):
+    """Batch slots in use the active scope names for plain (composite) job ``k``, or None."""
+    return _nth(_capture.used[composite], k) if _capture is not None and _capture.used is not None else None
+
+
+def indirect_for(ptr):
+    """Pointer-table entry address the active scope names for the dL/dcolor buffer at ``ptr``, or None."""
+    return _capture.grad_ind.get(ptr) if _capture is not None and _capture.grad_ind is not None else None
 
 
 def _f32c(t, name, device, memo=None):
@@ -497,8 +535,7 @@ def _fill_backward_job(a, settings, P, sh_M, inputs7, radii, ws_ptrs, capacity, 
     a.capacity = capacity
     g_color, g_depth, g_alpha = image_grads
     a.dL_dcolor, a.dL_ddepth, a.dL_dalpha = g_color.data_ptr(), _addr(g_depth), _addr(g_alpha)
-    if _capture_grad_ind is not None:
-        a.dL_dcolor_indirect = _capture_grad_ind.get(g_color.data_ptr())
+    a.dL_dcolor_indirect = indirect_for(a.dL_dcolor)
     a.grad_ws = grad_ws.data_ptr()
     a.dL_dmeans3D, a.dL_dmeans2D, a.dL_dcolors, a.dL_dopacity, a.dL_dscales, a.dL_drotations, a.dL_dcov3D, a.dL_dsh = \
         [_addr(t) for t in dgrads8]
@@ -510,7 +547,7 @@ N_IN = 8      # tensor arguments per job: means3D, means2D, sh, colors_precomp, 
 class _Rasterize(torch.autograd.Function):
     """K renders, one launch per pipeline stage.  apply(K, settings, grad_enabled, shared, densify, frozen, opts, *tensors[8 K]).
     ``opts``: None or a dict -- ``keep_keys``: the renders will be sources of composite renders (:class:`_Compose`): their
-    sorts keep the sorted 64-bit keys, and the host records of the jobs are published in ``_last_handles``.
+    sorts keep the sorted 64-bit keys, and the host records of the jobs are left in ``opts['handles']``.
     ``densify``: None or a K-list of None / (xyz_grad_accum, track_cnt, radius_max) tensors updated IN PLACE by that
     render's backward (fused densification statistics, include/exa_raster.h).
     ``frozen``: None or a K-list of None / 8-tuples in the order of ``_IN_NAMES``: a CONSTANT prefix of Gaussians that
@@ -520,7 +557,6 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, K, settings, grad_enabled, shared, densify, frozen, opts, *tensors):
-        global _last_handles
         lib = _lib.load()
         keep_keys = bool(opts and opts.get('keep_keys'))
         device = tensors[0].device
@@ -605,10 +641,7 @@ class _Rasterize(torch.autograd.Function):
                     _carve(j, (_capacity_for(j.key, k) + 63) // 64 * 64, device)
                 else:
                     _carve(j, 0, device, bins=False)
-                rep = reports[k] if reports is not None else None
-                if capturing and _capture_report is not None and k < len(_capture_report):
-                    rep = _capture_report[k]          # a reserved slot, read by the owner of the graph after each replay
-                _fill_forward_job(arr[k], j, rep)
+                _fill_forward_job(arr[k], j, report_for(k) if capturing else reports[k] if reports is not None else None)
 
             if mode == 'exact':
                 _lib.check(lib.exa_raster_forward_bin_batch(arr, K, stream))
@@ -646,7 +679,9 @@ class _Rasterize(torch.autograd.Function):
             _debug_last['bin'] = j.bins if getattr(j, 'bins', None) is not None else j.ws[j.gb + j.tb:]
             _debug_last['capacity'] = j.capacity
         if keep_keys:
-            _last_handles = jobs
+            opts['handles'] = jobs
+        if _capture is not None and _capture.jobs is not None:
+            _capture.jobs += jobs
         _tls.is_vis = [j.is_vis for j in jobs]
         ctx.need_ctx = need_ctx
         outs = []
@@ -743,9 +778,8 @@ class _Rasterize(torch.autograd.Function):
                     a.densify_grad_accum, a.densify_track_cnt, a.densify_radius_max = [_addr(t) for t in dens]
                 a.grad_first = nF
                 a.accumulate = 1 if fold else 0
-                a.used_slots = (j.need + 63) // 64 if j.need else 0
-                if _capture_used is not None and k < len(_capture_used[0]):
-                    a.used_slots = int(_capture_used[0][k])
+                used = used_for(k)               # (baked into a backward that is being recorded)
+                a.used_slots = int(used) if used is not None else (j.need + 63) // 64 if j.need else 0
                 if config.upstream_scale_grad and d_scales is not None and float(j.rs.scale_modifier) != 1.0:
                     keep.append((d_scales, float(j.rs.scale_modifier)))
                 ret += [d_means3D, d_means2D, d_sh, d_colors, d_opac, d_scales, d_rot, d_cov]
@@ -862,7 +896,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """``densify_stats``: optional ``(xyz_grad_accum, track_cnt, radius_max)`` float32 tensors of P elements that THIS
     render's backward updates in place (fused densification statistics, see ``densify.track_densify_stats``)."""
     dens = None if densify_stats is None else [_check_densify(densify_stats, int(means3D.shape[0]), means3D.device)]
-    if config.compiled_node != 'off' and isinstance(raster_settings, tuple) and _capture_report is None:
+    if config.compiled_node != 'off' and isinstance(raster_settings, tuple) and _capture is None:
         out = _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                   raster_settings, dens[0] if dens else None)
         if out is not None:
@@ -914,13 +948,11 @@ def rasterize_gaussians_batch(jobs, keep_keys=False):
     if any(j.get('densify_stats') is not None for j in jobs):
         dens = [_check_densify(j.get('densify_stats'), int(j['means3D'].shape[0]), j['means3D'].device) for j in jobs]
         _check_densify_aliasing(dens, shared)
-    global _last_handles
-    _last_handles = None
-    outs = _Rasterize.apply(K, tuple(j['raster_settings'] for j in jobs), torch.is_grad_enabled(), shared, dens, frozen,
-                            {'keep_keys': True} if keep_keys else None, *flat)
+    opts = {'keep_keys': True} if keep_keys else None
+    outs = _Rasterize.apply(K, tuple(j['raster_settings'] for j in jobs), torch.is_grad_enabled(), shared, dens, frozen, opts, *flat)
     res = [tuple(outs[4 * k: 4 * k + 4]) for k in range(K)]
     if keep_keys:
-        handles, _last_handles = _Handles(_last_handles), None
+        handles = _Handles(opts['handles'])
         handles.token = outs[4 * K]
         ref = weakref.ref(handles.token)       # (weak: job -> token -> grad_fn -> ctx -> job would keep the workspaces alive)
         for j in handles:

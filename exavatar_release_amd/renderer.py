@@ -14,6 +14,7 @@ import warnings
 import torch
 import torch.nn as nn
 
+from ._device import warm_up
 from .camera import make_raster_matrices
 from .rasterizer import (GaussianRasterizationSettings, rasterize_composites, rasterize_gaussians,
                          rasterize_gaussians_batch, take_is_vis)
@@ -495,45 +496,30 @@ class GraphedRenderer:
 
     def _capture(self, tan):
         from . import rasterizer as rz
-        saved = (rz.config.mode, rz.config.fixed_capacity, rz.config.keep_debug, rz.config.on_overflow)
-        rz.config.on_overflow = 'retry'       # (the eager warm-up below repairs an overflow whatever the user's policy: the graph has its own path)
-        try:
-            with torch.no_grad():
-                if self._capacity is None:                    # measure this frame once with the two-stage protocol
-                    rz.config.mode, rz.config.fixed_capacity = 'exact', None
-                    rz.config.keep_debug = True
-                    self._raster(tan)
-                    need = rz.read_header(rz._debug_last['tile'])[0]
-                    self._capacity = max(int(need * self.growth), 1 << 16)
-                self._capacity = (self._capacity + 63) // 64 * 64
-                rz.config.mode, rz.config.fixed_capacity, rz.config.keep_debug = 'capacity', self._capacity, True
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):                 # warm-up on a side stream, as torch.cuda.graph asks for
-                    self._raster(tan)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                torch.cuda.synchronize(self.device)
-                # the captured call reports its header into ONE pinned host slot (a plain store from the scatter kernel,
-                # include/exa_raster.h: host_header): every replay rewrites it, the host resets the tag before a replay and
-                # polls it afterwards -- no read-back, no synchronisation per frame
-                self._drop_slot()                             # the graph that wrote into it is gone
-                pool = rz._pool()
-                got = pool.reserve() if pool is not None else None   # outside the ring eager renders draw from
-                if got is not None:
-                    self._slot = (got[0], got[1])
-                    rz._capture_report = [self._slot]
-                try:
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph):
-                        self._outs = self._raster(tan)
-                finally:
-                    rz._capture_report = None
-                self._tile = rz._debug_last['tile']           # the captured call's tile workspace (graph-private pool)
-                rz._debug_last.clear()
-                self._tan = tan
-                self.captures += 1
-        finally:
-            rz.config.mode, rz.config.fixed_capacity, rz.config.keep_debug, rz.config.on_overflow = saved
+        # ('retry': the eager warm-up below repairs an overflow whatever the user's policy; the graph has its own path)
+        with rz.capture_scope(jobs=[], on_overflow='retry') as scope, torch.no_grad():
+            if self._capacity is None:                    # measure this frame once with the two-stage protocol
+                rz.config.mode, rz.config.fixed_capacity = 'exact', None
+                self._raster(tan)
+                self._capacity = max(int(scope.jobs[-1].need * self.growth), 1 << 16)
+            self._capacity = (self._capacity + 63) // 64 * 64
+            rz.config.mode, rz.config.fixed_capacity = 'capacity', self._capacity
+            warm_up(self.device, lambda: self._raster(tan))
+            # the captured call reports its header into ONE pinned host slot (a plain store from the scatter kernel,
+            # include/exa_raster.h: host_header): every replay rewrites it, the host resets the tag before a replay and
+            # polls it afterwards -- no read-back, no synchronisation per frame
+            self._drop_slot()                             # the graph that wrote into it is gone
+            pool = rz._pool()
+            if pool is not None:
+                self._slot = pool.reserve()[:2]               # outside the ring eager renders draw from
+                scope.report = [self._slot]
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                self._outs = self._raster(tan)
+            j = scope.jobs[-1]
+            self._tile = j.ws[j.gb:j.gb + j.tb]           # the captured call's tile workspace (graph-private pool)
+            self._tan = tan
+            self.captures += 1
 
     def __call__(self, gaussian_assets, cam_param, bg=None):
         from . import rasterizer as rz

@@ -413,3 +413,51 @@ def test_closing_graphed_objects_gives_every_reserved_report_slot_back(dev):
     gr.close()
     it.close()
     assert len(pool.free_reserved) == n0 and len(set(pool.free_reserved)) == n0
+
+
+def test_a_capture_that_fails_leaves_no_scope_no_config_and_no_report_slot_behind(dev):
+    """``loss_fn`` hands back a non-scalar INSIDE the recording (its second call; the first is the eager warm-up): ``_capture``
+    raises its ValueError after ``render_iteration`` has returned -- every forked stream has joined, ``torch.cuda.graph`` ends the
+    capture on its way out.  Nothing of the failed capture stays: the capture scope is gone, ``config`` is what it was, the
+    reserved report slots are back, single renders take the compiled node again and the next object captures as if nothing
+    had happened."""
+    from exavatar_release_amd import rasterizer as rz
+    G = _G(dev, 15)
+    calls = []
+
+    def good(out, w):
+        return sum((out[n]['img'] * G[k]).sum() * w[k] for k, n in enumerate(exa.ITERATION_RENDERS))
+
+    def bad(out, w):
+        calls.append(1)
+        return good(out, w) if len(calls) == 1 else out['scene']['img'] * w[0]
+    sets = _sets(1500, 800, 121, dev)
+    cam, bg, w = _cam(2, dev), torch.full((3,), 0.4, device=dev), torch.rand(5, device=dev)
+    rend = exa.GaussianRenderer()
+    human = {k: v.detach().clone() for k, v in sets[1].items()}
+    rend(human, (H, W), cam, bg)                   # (first call of the shape: the condition of tests/test_gpu_reference_renderer.py)
+    pool = rz._pool()
+    assert pool is not None
+    gc.collect()                                   # (objects earlier tests left to the collector give their slots back now, not below)
+    n_free = len(pool.free_reserved)
+    before = (exa.config.mode, exa.config.fixed_capacity, exa.config.on_overflow)
+    it = exa.GraphedIteration((H, W), dev, loss_fn=bad)
+    with pytest.raises(ValueError, match='must return a scalar'):
+        it(*_leaves(sets), cam, bg, None, loss_args=(w,))
+    assert len(calls) == 2
+    assert rz._capture is None
+    assert (exa.config.mode, exa.config.fixed_capacity, exa.config.on_overflow) == before
+    it.close()
+    assert len(pool.free_reserved) == n_free and len(set(pool.free_reserved)) == n_free
+    n0 = rz.compiled_calls
+    out = rend(human, (H, W), cam, bg)
+    assert rz.compiled_calls == n0 + 1, (rz._compiled.last_decline() if rz._compiled else rz._compiled, exa.config.__dict__, rz._capture)
+    assert bool(torch.isfinite(out['img']).all())
+    eager = _eager()
+    with exa.GraphedIteration((H, W), dev, loss_fn=good) as fresh:
+        da, db = _stats(1500, dev), _stats(1500, dev)
+        for i in range(2):
+            pa, la, ga = _run_loss(fresh, True, good, sets, _cam(2 + i, dev), bg, da, (w,))
+            pb, lb, gb = _run_loss(eager, False, good, sets, _cam(2 + i, dev), bg, db, (w,))
+            _same(pa, pb, 'plane'); _same([la], [lb], 'loss'); _same(ga, gb, 'grad'); _same(da, db, 'densify statistic')
+        assert fresh.captures == 1

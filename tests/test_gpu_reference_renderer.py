@@ -35,7 +35,7 @@ def test_hip_renderer_matches_the_reference_callers_outputs(golden_dir, name):
         assert sorted(out) == ['depthmap', 'img', 'is_vis', 'mask', 'mean_2d', 'radius']
         (out['img'] * G).sum().backward()
         if rep:
-            assert rz.compiled_calls == n0 + 1, (rz._compiled.last_decline() if rz._compiled else rz._compiled, exa.config.__dict__, rz._capture_report)
+            assert rz.compiled_calls == n0 + 1, (rz._compiled.last_decline() if rz._compiled else rz._compiled, exa.config.__dict__, rz._capture)
         assert torch.equal(out['radius'].cpu(), torch.from_numpy(gold[p + 'radius']))          # int32, bit-equal
         assert out['radius'].dtype == torch.int32 and out['is_vis'].dtype == torch.bool
         assert torch.equal(out['is_vis'].cpu(), torch.from_numpy(gold[p + 'is_vis']))

@@ -88,19 +88,78 @@ def test_fill_backward_job_names_every_tensor_and_leaves_the_callers_fields_zero
     assert (a.densify_grad_accum, a.densify_track_cnt, a.densify_radius_max) == (None, None, None)
 
 
-def test_fill_backward_job_looks_up_the_indirect_colour_gradient_while_a_backward_is_recorded(monkeypatch):
+def test_fill_backward_job_looks_up_the_indirect_colour_gradient_while_a_backward_is_recorded():
     """``dL_dcolor_indirect``: the pointer-table entry a recorded backward reads dL/dcolor through, found by the address of the
-    colour gradient in ``_capture_grad_ind``; a gradient the table does not name gets none."""
+    colour gradient in the capture scope's ``grad_ind``; a gradient the table does not name gets none."""
     P, H, W = 3, 4, 6
     inputs7 = (torch.zeros(P, 3), None, torch.zeros(P, 3), torch.zeros(P, 1), torch.zeros(P, 3), torch.zeros(P, 4), None)
     radii, grad_ws = torch.zeros(P, dtype=torch.int32), torch.zeros(64, dtype=torch.uint8)
     known, other = torch.zeros(3, H, W), torch.zeros(3, H, W)
-    monkeypatch.setattr(rz, '_capture_grad_ind', {known.data_ptr(): 0x7000})
-    for g_color, expect in ((known, 0x7000), (other, None)):
-        arr = (_lib.ExaRasterBackwardJob * 1)()
-        rz._fill_backward_job(arr[0], _lib.ExaRasterSettings(), P, 0, inputs7, radii, (64, 128, 192), 64, (g_color, None, None),
-                              grad_ws, [None] * 8)
-        assert arr[0].dL_dcolor == g_color.data_ptr() and arr[0].dL_dcolor_indirect == expect
+    with rz.capture_scope(grad_ind={known.data_ptr(): 0x7000}):
+        for g_color, expect in ((known, 0x7000), (other, None)):
+            arr = (_lib.ExaRasterBackwardJob * 1)()
+            rz._fill_backward_job(arr[0], _lib.ExaRasterSettings(), P, 0, inputs7, radii, (64, 128, 192), 64, (g_color, None, None),
+                                  grad_ws, [None] * 8)
+            assert arr[0].dL_dcolor == g_color.data_ptr() and arr[0].dL_dcolor_indirect == expect
+
+
+# ---- the capture scope ---------------------------------------------------------------------------------------------------
+def _nothing_held():
+    return [rz.report_for(0), rz.report_for(0, True), rz.used_for(0), rz.used_for(0, True), rz.indirect_for(0x10)]
+
+
+def test_capture_scope_accessors_return_what_was_put_in_and_none_elsewhere():
+    assert rz._capture is None and _nothing_held() == [None] * 5          # no scope is active
+    with rz.capture_scope(report=[(9, 1), None], report_c=[None, (11, 3)], used=([4, 5, 6], [7]), grad_ind={0x10: 0x7000}) as scope:
+        assert rz._capture is scope and scope.jobs is None
+        assert [rz.report_for(k) for k in range(3)] == [(9, 1), None, None]          # an entry, a None entry, past the end
+        assert [rz.report_for(k, True) for k in range(3)] == [None, (11, 3), None]
+        assert [rz.used_for(k) for k in range(4)] == [4, 5, 6, None]
+        assert [rz.used_for(k, True) for k in range(2)] == [7, None]
+        assert rz.indirect_for(0x10) == 0x7000 and rz.indirect_for(0x20) is None
+        scope.report = [(10, 2)]                                                     # fields may be assigned in the body
+        assert rz.report_for(0) == (10, 2) and rz.report_for(1) is None
+    assert rz._capture is None and _nothing_held() == [None] * 5
+    with rz.capture_scope(jobs=[]) as scope:                                         # every field left out: nothing is held
+        assert _nothing_held() == [None] * 5 and scope.jobs == []
+    assert rz._capture is None
+
+
+def test_capture_scope_restores_config_and_removes_itself_on_every_kind_of_exit():
+    cfg = rz.config
+    entry = (cfg.mode, cfg.fixed_capacity, cfg.on_overflow, dict(vars(cfg)))
+    state = lambda: (cfg.mode, cfg.fixed_capacity, cfg.on_overflow, dict(vars(cfg)))          # noqa: E731
+    other = 'raise' if cfg.on_overflow == 'retry' else 'retry'
+    with rz.capture_scope(mode='exact', fixed_capacity=None, on_overflow=other):                # a normal exit
+        assert (cfg.mode, cfg.fixed_capacity, cfg.on_overflow) == ('exact', None, other)
+    assert state() == entry and rz._capture is None
+    with pytest.raises(KeyError, match='from the body'):                                        # an exception in the body
+        with rz.capture_scope(mode='capacity', fixed_capacity=[64, 128]):
+            assert (cfg.mode, cfg.fixed_capacity) == ('capacity', [64, 128])
+            raise KeyError('from the body')
+    assert state() == entry and rz._capture is None
+    with rz.capture_scope(mode='exact', on_overflow=other):                                     # the body reassigns, as
+        cfg.mode, cfg.fixed_capacity = 'capacity', [192]                                        # GraphedIteration._capture does
+        assert (cfg.mode, cfg.fixed_capacity) == ('capacity', [192])
+    assert state() == entry and rz._capture is None
+    with rz.capture_scope(report=[(9, 1)], mode='exact') as outer:                              # scopes do not nest
+        with pytest.raises(RuntimeError, match='already active'):
+            with rz.capture_scope(report=[(10, 2)], mode='capacity'):
+                raise AssertionError('the inner body ran')
+        assert rz._capture is outer and rz.report_for(0) == (9, 1) and cfg.mode == 'exact'      # the first scope is intact
+    assert state() == entry and rz._capture is None
+
+
+def test_capture_scope_is_seen_from_another_thread():
+    """``torch.autograd.grad`` inside a capture runs ``_Rasterize.backward`` / ``_Compose.backward`` on autograd's device thread:
+    the scope is process-wide, not thread-local."""
+    import threading
+    seen = []
+    with rz.capture_scope(used=([3], []), grad_ind={0x10: 0x7000}) as scope:
+        t = threading.Thread(target=lambda: seen.append((rz._capture, rz.used_for(0), rz.indirect_for(0x10))))
+        t.start()
+        t.join()
+    assert len(seen) == 1 and seen[0][0] is scope and seen[0][1:] == (3, 0x7000)
 
 
 def test_image_grads_fill_in_a_missing_colour_and_keep_missing_planes_none():
