@@ -57,6 +57,11 @@ reference ``avatar/common/nets/loss.py:148-197``, ``avatar/common/utils/smpl_x.p
 ``avatar/main/model.py:223,249-251``):
 
     from exavatar_release_amd import ArmRGBReg, HandRGBReg, HandMeanReg, get_arm
+
+and for the scene side in front of the rasterizer (the body of ``SceneGaussian.forward``: activations, the 6D rotation ->
+quaternion route and the SH colour seen from the camera centre, reference ``avatar/common/nets/module.py:253-272``):
+
+    from exavatar_release_amd import scene_assets
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -75,6 +80,7 @@ from .blend_shapes import BlendShapes, BlendTable, blend_offsets
 from .kinematics import batch_rigid_transform, joint_transforms
 from .body import BodyOutput, BodyTemplate, MeshUpsampler
 from .vertex_regs import ArmPlan, ArmRGBReg, HandMeanReg, HandRGBReg, arm_neighbors, arm_rgb_loss, get_arm
+from .scene_assets import scene_assets
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -83,4 +89,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'vertex_normals', 'shade_mesh', 'render_mesh', 'knn_points', 'TriplaneFeatures',
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
-           'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm']
+           'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
+           'scene_assets']

@@ -225,6 +225,9 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
     'exa_raster_store_pointers': (ctypes.c_int, [c_void_p, ctypes.POINTER(c_void_p), _I32, c_void_p]),
     'exa_raster_mark_visible': (ctypes.c_int, [_SP, _I32, c_void_p, c_void_p, c_void_p]),
     'exa_raster_densify_stats': (ctypes.c_int, [_I32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the scene-Gaussian stage (csrc/scene_assets.hip)
+    'exa_raster_scene_assets_forward': (ctypes.c_int, [_I32, _I32, _I32] + [c_void_p] * 13),
+    'exa_raster_scene_assets_backward': (ctypes.c_int, [_I32, _I32, _I32] + [c_void_p] * 19),
     'exa_ssim_forward': (ctypes.c_int, [_I32, _I32, _I32] + [c_void_p] * 7),
     'exa_ssim_backward': (ctypes.c_int, [_I32, _I32, _I32] + [c_void_p] * 8),
     'exa_photo_loss_blocks': (ctypes.c_int64, [_I32, _I32, _I32, _I32]),

@@ -645,6 +645,59 @@ int exa_raster_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t*
     return 0;
 }
 
+static int check_scene(int32_t P, int32_t Mr, int32_t sh_degree) {
+    if (P < 0) return fail(EXA_RASTER_E_INVALID, "scene_assets: P < 0");
+    if (Mr != 0 && Mr != 3 && Mr != 8 && Mr != 15)
+        return fail(EXA_RASTER_E_INVALID, "scene_assets: Mr (rows of feature_rest) must be 0, 3, 8 or 15");
+    if (sh_degree < 0 || sh_degree > 3) return fail(EXA_RASTER_E_INVALID, "scene_assets: sh_degree must be 0 .. 3");
+    if ((sh_degree + 1) * (sh_degree + 1) > 1 + Mr)
+        return fail(EXA_RASTER_E_INVALID, "scene_assets: sh_degree needs (sh_degree + 1)^2 <= 1 + Mr coefficients");
+    return 0;
+}
+
+int exa_raster_scene_assets_forward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* opacity,
+                                    const float* scale, const float* rotation, const float* feature_dc,
+                                    const float* feature_rest, const float* cam_R, const float* cam_t,
+                                    float* opacity_out, float* scale_out, float* rotation_out, float* rgb,
+                                    void* stream) {
+    if (int rc = check_scene(P, Mr, sh_degree)) return rc;
+    if (P == 0) return 0;
+    if (!mean || !opacity || !scale || !rotation || !feature_dc || (Mr > 0 && !feature_rest))
+        return fail(EXA_RASTER_E_NULLPTR, "scene_assets: a parameter array is NULL");
+    if (!cam_R || !cam_t) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: cam_R / cam_t is NULL");
+    if (!opacity_out || !scale_out || !rotation_out || !rgb)
+        return fail(EXA_RASTER_E_NULLPTR, "scene_assets: an output array is NULL");
+    EXA_HIP(launch_scene_assets_fwd(P, Mr, sh_degree, mean, opacity, scale, rotation, feature_dc, feature_rest, cam_R,
+                                    cam_t, opacity_out, scale_out, rotation_out, rgb, static_cast<hipStream_t>(stream)),
+            "scene_fwd");
+    return 0;
+}
+
+int exa_raster_scene_assets_backward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* rotation,
+                                     const float* feature_dc, const float* feature_rest, const float* cam_R,
+                                     const float* cam_t, const float* opacity_out, const float* scale_out,
+                                     const float* grad_opacity_out, const float* grad_scale_out,
+                                     const float* grad_rotation_out, const float* grad_rgb, float* grad_mean,
+                                     float* grad_opacity, float* grad_scale, float* grad_rotation,
+                                     float* grad_feature_dc, float* grad_feature_rest, void* stream) {
+    if (int rc = check_scene(P, Mr, sh_degree)) return rc;
+    if (Mr == 0) grad_feature_rest = nullptr;
+    if (P == 0 || (!grad_mean && !grad_opacity && !grad_scale && !grad_rotation && !grad_feature_dc && !grad_feature_rest))
+        return 0;
+    if (grad_opacity && !opacity_out) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_opacity needs opacity_out");
+    if (grad_scale && !scale_out) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_scale needs scale_out");
+    if (grad_rotation && !rotation) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_rotation needs rotation");
+    if ((grad_mean || grad_feature_dc || grad_feature_rest) &&
+        (!mean || !feature_dc || (Mr > 0 && !feature_rest) || !cam_R || !cam_t))
+        return fail(EXA_RASTER_E_NULLPTR,
+                    "scene_assets: the colour gradients need mean, feature_dc, feature_rest, cam_R and cam_t");
+    EXA_HIP(launch_scene_assets_bwd(P, Mr, sh_degree, mean, rotation, feature_dc, feature_rest, cam_R, cam_t, opacity_out,
+                                    scale_out, grad_opacity_out, grad_scale_out, grad_rotation_out, grad_rgb, grad_mean,
+                                    grad_opacity, grad_scale, grad_rotation, grad_feature_dc, grad_feature_rest,
+                                    static_cast<hipStream_t>(stream)), "scene_bwd");
+    return 0;
+}
+
 int exa_ssim_forward(int32_t N, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_map,
                      float* dm_dmu1, float* dm_dE11, float* dm_dE12, void* stream) {
     if (N < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");

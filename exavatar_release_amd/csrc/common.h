@@ -560,5 +560,15 @@ hipError_t launch_l1(int B, int C, int H, int W, const int* crop, const float* x
                      const float* bg, const float* g, float* out, int backward, hipStream_t s);
 hipError_t launch_densify_stats(int P, const float* g2d, const int32_t* radii, float* accum, float* cnt, float* rmax,
                                 hipStream_t s);
+// scene_assets.hip: the scene-Gaussian stage (sizes and the degree are the caller's to check)
+hipError_t launch_scene_assets_fwd(int P, int Mr, int deg, const float* mean, const float* opacity, const float* scale,
+                                   const float* rotation, const float* dc, const float* rest, const float* cam_R,
+                                   const float* cam_t, float* opacity_out, float* scale_out, float* rotation_out,
+                                   float* rgb, hipStream_t s);
+hipError_t launch_scene_assets_bwd(int P, int Mr, int deg, const float* mean, const float* rotation, const float* dc,
+                                   const float* rest, const float* cam_R, const float* cam_t, const float* opacity_out,
+                                   const float* scale_out, const float* g_opacity_out, const float* g_scale_out,
+                                   const float* g_rotation_out, const float* g_rgb, float* g_mean, float* g_opacity,
+                                   float* g_scale, float* g_rotation, float* g_dc, float* g_rest, hipStream_t s);
 
 }  // namespace exa

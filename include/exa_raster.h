@@ -374,6 +374,75 @@ int exa_raster_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t*
                              float* xyz_grad_accum, float* track_cnt, float* radius_max, void* stream);
 
 /*
+ * The scene-Gaussian stage: SceneGaussian.forward (reference avatar/common/nets/module.py:253-272) in one launch each
+ * way -- what turns the scene's parameters into the asset dict the rasterizer takes, per sample.  All arrays [dev],
+ * fp32, contiguous: mean [P,3], opacity [P,1] (logits), scale [P,3] (logs), rotation [P,6], feature_dc [P,1,3],
+ * feature_rest [P,Mr,3] with Mr in {0, 3, 8, 15} (NULL when Mr = 0), cam_R [3,3], cam_t [3].  sh_degree is 0 .. 3 with
+ * (sh_degree + 1)^2 <= 1 + Mr.  `mean` passes through untouched (the asset's mean_3d is the caller's own array).
+ * Every line is one rounded fp32 operation, never fused, sums in the order written; only + - * / sqrt occur outside the
+ * two activations, so a float32 restatement on a CPU gives the same bits.  With eps = 1e-12:
+ *   opacity_out [P,1] = 1 / (1 + expf(-opacity));  scale_out [P,3] = expf(scale).
+ *   rotation_out [P,4], quaternion (w, x, y, z), with a1 = rotation[0:3], a2 = rotation[3:6]:
+ *     n1 = sqrt((a1x a1x + a1y a1y) + a1z a1z), b1 = a1 / max(n1, eps);  dot = (b1x a2x + b1y a2y) + b1z a2z;
+ *     c = a2 - dot b1;  n2 = |c| likewise, b2 = c / max(n2, eps);
+ *     b3 = (b1y b2z - b1z b2y, b1z b2x - b1x b2z, b1x b2y - b1y b2x);  m = rows (b1, b2, b3).
+ *     x0 = ((1 + m00) + m11) + m22, x1 = ((1 + m00) - m11) - m22, x2 = ((1 - m00) + m11) - m22,
+ *     x3 = ((1 - m00) - m11) + m22;  i = the first index of their maximum;  q = sqrt(x_i), D = 2 q.
+ *     With A = m21 - m12, B = m02 - m20, C = m10 - m01, E = m10 + m01, F = m02 + m20, G = m12 + m21:
+ *       row_0 = (q q, A, B, C), row_1 = (A, q q, E, F), row_2 = (B, E, q q, G), row_3 = (C, F, G, q q);
+ *     out = row_i / D, negated when out[0] < 0.
+ *     The four x sum to 4, so the selected one is >= 1: the 0.1 floor under q and the positive-part branch of the
+ *     square root in pytorch3d's matrix_to_quaternion can never bind for the selected candidate and are not carried.
+ *     A zero row gives (0.5, 0, 0, 0); (0, 1, 0, 0, 0, 1) is a four-way tie and gives (0.5, -0.5, -0.5, -0.5).
+ *   rgb [P,3]:
+ *     cam_pos = inverse(cam_R) (-cam_t) by cofactors, on the device (one lane per workgroup): c_ij the cofactors of
+ *     cam_R, each `p q - r s`, det = (R00 c00 + R01 c01) + R02 c02,
+ *     cam_pos_i = ((c_0i / det) (-t0) + (c_1i / det) (-t1)) + (c_2i / det) (-t2).
+ *     v = mean - cam_pos, n = sqrt((vx vx + vy vy) + vz vz), (x, y, z) = v / max(n, eps).
+ *     Per channel, with sh_0 = feature_dc and sh_k = feature_rest[k - 1]: the polynomial of the reference's eval_sh
+ *     (avatar/common/utils/transforms.py:112-155) in its term order and association,
+ *       res = C0 sh_0;  res = res - b1 sh_1;  res = res + b2 sh_2;  res = res - b3 sh_3;  res = res + b_k sh_k, k = 4 ..
+ *     with b1 = C1 y, b2 = C1 z, b3 = C1 x, b4 = C2[0] (x y), b5 = C2[1] (y z), b6 = C2[2] ((2 zz - xx) - yy),
+ *     b7 = C2[3] (x z), b8 = C2[4] (xx - yy), b9 = (C3[0] y) (3 xx - yy), b10 = (C3[1] (x y)) z,
+ *     b11 = (C3[2] y) ((4 zz - xx) - yy), b12 = (C3[3] z) ((2 zz - 3 xx) - 3 yy), b13 = (C3[4] x) ((4 zz - xx) - yy),
+ *     b14 = (C3[5] z) (xx - yy), b15 = (C3[6] x) (xx - 3 yy);  u = res + 0.5;  rgb = u < 0 ? 0 : u.
+ * exa_raster_scene_assets_backward: one launch, no atomics (nothing is summed across Gaussians), the same bits for the
+ * same inputs.  A NULL cotangent (grad_*_out, grad_rgb) counts as zero; a NULL gradient is not computed; every
+ * element of every requested gradient is written, zeros included (the rows of grad_feature_rest above the active
+ * degree get exactly +0), so the arrays may arrive uninitialised.
+ *   grad_opacity = (g (1 - y)) y and grad_scale = g y from the saved outputs y.
+ *   out = v / max(n, eps) backward, used three times (a1, c, the view direction), for a cotangent g:
+ *     s = (g0 v0 + g1 v1) + g2 v2;  gd = -(s / (d d)), d = max(n, eps);  gn = n >= eps ? gd : 0;
+ *     k = n > 0 ? gn / n : 0;  gv_j = g_j / d + v_j k        (torch's clamp_min and norm conventions).
+ *   grad_rotation: no gradient through i or the sign.  gs = the cotangent, negated where out was;  gr_j = gs_j / D;
+ *     S = ((gs0 row0 + gs1 row1) + gs2 row2) + gs3 row3;  gD = -(S / (D D));  gq = 2 gD + (gr_i 2) q;  gx = gq / D;
+ *     dL/dm00, dL/dm11, dL/dm22 = +-gx by x_i's signs; dL/dm21 = gA + gG, dL/dm12 = gG - gA, dL/dm02 = gB + gF,
+ *     dL/dm20 = gF - gB, dL/dm10 = gC + gE, dL/dm01 = gE - gC with gA .. gG the gr_j of row_i's entries (0 if absent);
+ *     gb1 = gb1 + b2 x gb3, gb2 = gb2 + gb3 x b1 (each component `cur + (p q - r s)`);  gc = backward of b2 at gb2;
+ *     gdot = -((gc0 b1x + gc1 b1y) + gc2 b1z);  gb1_j = (gb1_j - dot gc_j) + gdot a2_j;  grad a2_j = gc_j + gdot b1_j;
+ *     grad a1 = backward of b1 at gb1.  A zero row gets finite values (of order 1 / eps), as torch gives.
+ *   The colour: gm = grad_rgb where u >= 0, else 0 (clamp_min passes the gradient at equality).
+ *     grad_feature_dc = C0 gm;  grad sh_k = b_k gm, negated for k = 1, 3;
+ *     w_k = (gm_r sh_k,r + gm_g sh_k,g) + gm_b sh_k,b, negated for k = 1, 3;  dL/d(x, y, z) = the sum over k of
+ *     w_k d b_k / d(x, y, z) in ascending k (csrc/scene_assets.hip writes the derivative terms out);
+ *     grad_mean = backward of the view direction at that -- the view-direction term only: what reaches mean_3d itself
+ *     is the caller's (autograd's) to add.
+ * A negative P, an Mr or sh_degree outside the above: EXA_RASTER_E_INVALID before any device call.
+ */
+int exa_raster_scene_assets_forward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* opacity,
+                                    const float* scale, const float* rotation, const float* feature_dc,
+                                    const float* feature_rest, const float* cam_R, const float* cam_t,
+                                    float* opacity_out, float* scale_out, float* rotation_out, float* rgb,
+                                    void* stream);
+int exa_raster_scene_assets_backward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* rotation,
+                                     const float* feature_dc, const float* feature_rest, const float* cam_R,
+                                     const float* cam_t, const float* opacity_out, const float* scale_out,
+                                     const float* grad_opacity_out, const float* grad_scale_out,
+                                     const float* grad_rotation_out, const float* grad_rgb, float* grad_mean,
+                                     float* grad_opacity, float* grad_scale, float* grad_rotation,
+                                     float* grad_feature_dc, float* grad_feature_rest, void* stream);
+
+/*
  * Fused SSIM map (the image-loss gradient producer in front of the rasterizer's backward).
  * Replaces class SSIM of reference avatar/common/nets/loss.py:31-74 -- five grouped 11x11 conv2d (Gaussian window,
  * sigma 1.5, zero padding 5) + elementwise ops + their autograd graph -- for N = batch * channels planes of H x W
