@@ -205,6 +205,14 @@ __host__ __device__ inline int num_chunks(int P) { return (P + CHUNK - 1) / CHUN
 #define EXA_BIN_PARTS 4
 #endif
 constexpr int BIN_PARTS = EXA_BIN_PARTS;   // workgroups per cell in the sub-tile binning (binning.hip)
+// Lists of up to WAVE_KEYS keys are sorted by ONE wave of the sort launch, four lists per workgroup (render_fwd.hip); the
+// longer ones get a workgroup each, found through the batch owners of the bin workspace.  Build-time variant: 256 or 512;
+// 0 builds the launch of one workgroup per sub-tile.
+#ifndef EXA_WAVE_KEYS
+#define EXA_WAVE_KEYS 512
+#endif
+constexpr int WAVE_KEYS = EXA_WAVE_KEYS;
+static_assert(WAVE_KEYS == 0 || WAVE_KEYS == 256 || WAVE_KEYS == 512, "EXA_WAVE_KEYS: 0, 256 or 512");
 struct TileWs {
     ExaRasterHeader* header;          // [1]          written by cell_scan_kernel
     uint32_t* cls_cur;                // [8][64]  launch-order slots handed out per (XCD region, list-length class) (zeroed by cell_scan)

@@ -3,11 +3,15 @@
 // The blend runs ONE WAVE per 8x8-pixel sub-tile (lane l -> pixel (l & 7, l >> 3)), one wave per workgroup,
 // no __syncthreads: a wave owns its list, its LDS slice and its 64 pixels, and frees its slot the moment
 // it is done.  Split in two launches so each gets the shape it needs:
-//   sort_subtiles_kernel  (256 threads, 16 KiB LDS): four waves co-operate on one sub-tile's bucket of
-//       (depth bits << 32 | id) keys -- rank sorted runs of 64 merged by rank (binary search) in place in
-//       LDS; lists > 2048 keys fall back to a register rank sort -- and write the sorted ids.
-//       Third radix digit of the binning (binning.hip).  Its first 16 workgroups build the length-sorted
-//       launch order of the blend.
+//   sort_subtiles_quads_kernel  (256 threads, 24 KiB LDS): sorts every sub-tile's bucket of (depth bits << 32 | id) keys
+//       and writes the sorted ids.  Third radix digit of the binning (binning.hip).  Lists of up to WAVE_KEYS keys
+//       (common.h) take ONE WAVE each, four lists per workgroup, no barrier: a rank sort up to 64 keys, a distribution
+//       sort in the wave's quarter of the LDS above that.  The longer lists -- found through the batch owners of the
+//       bin workspace -- take a workgroup each: the same distribution sort with four waves, a merge sort (rank sorted runs of 64 merged
+//       by binary search, in place) when the depths pile up in one bucket, a register rank sort beyond 2048 keys.  Its
+//       first 32 workgroups build the launch orders of the two blends.  Images of >= SPLIT_SORT_SUBTILES sub-tiles
+//       (and builds with WAVE_KEYS = 0) take sort_subtiles_kernel, one workgroup per list, with sort_short_kernel
+//       for the lists of one wave.
 //   render_fwd_kernel     (2.5 KiB LDS / wave): streams the sorted ids in batches of 64; each lane gathers ONE
 //       64-byte splat record (48 B used) into the wave's LDS slice, SoA -- ids are fetched two batches ahead
 //       and records one batch ahead, so the two dependent global round trips hide behind the blend of the
@@ -242,6 +246,116 @@ __device__ __forceinline__ void wave_rank_sort64(const unsigned long long* gkeys
     if (lane < n) {
         sorted[rank] = (uint32_t)mine;
         if (keys_out) keys_out[rank] = mine;                  // (the wave's loads are complete: rank depends on all of them)
+    }
+}
+
+// ---- one wave, one list of 65 .. 64 * E keys (E keys per lane): the distribution sort of lds_bucket_sort without a barrier --
+// The wave owns `buf` (64 * E keys) and `cnt` (64 * E counters) -- 12 bytes of LDS per key -- and the phases are separated by
+// wave_lds_fence(): the LDS operations of one wave execute in order.  Same exact order (depth bits, id), same escape: a
+// bucket with more than BUCKET_MAX keys (depths that pile up) -> nothing has been written yet, and the wave rank sorts the
+// list against its LDS-staged copy instead: n / 2 broadcast reads with 2 E compares each, slow (a 512-key list at one depth:
+// ~12 k instructions) and rare.  Bucket and arrival slot share a word (both < 2^16): eight registers less for E = 8.
+template <int E>
+__device__ __forceinline__ void wave_rank_sort_staged(const unsigned long long (&key)[E], int n, uint32_t* __restrict__ sorted,
+                                                      unsigned long long* keys_out, unsigned long long* buf, int lane) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) buf[e * 64 + lane] = key[e];     // (+inf pads included: the pair reads below end on one)
+    wave_lds_fence();
+    uint32_t rank[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) rank[e] = 0u;
+    const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(buf);
+#pragma unroll 2
+    for (int j = 0; j < (n + 1) / 2; ++j) {
+        const ulonglong2 kk = s2[j];                              // uniform address: LDS broadcast read
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            rank[e] += (kk.x < key[e]) ? 1u : 0u;
+            rank[e] += (kk.y < key[e]) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e * 64 + lane < n) {
+            sorted[rank[e]] = (uint32_t)key[e];
+            if (keys_out) keys_out[rank[e]] = key[e];             // in place over the input: all keys sit in registers
+        }
+    }
+}
+
+template <int E>
+__device__ __forceinline__ void wave_bucket_sort(const unsigned long long* gkeys, int n, uint32_t* __restrict__ sorted,
+                                                 unsigned long long* keys_out, unsigned long long* buf, uint32_t* cnt, int lane) {
+    constexpr int NB = 64 * E;
+    unsigned long long key[E];
+    uint32_t dmin = 0xffffffffu, dmax = 0u;
+    // (all E loads first, their first use in a loop of its own: see lds_bucket_sort)
+#pragma unroll
+    for (int e = 0; e < E; ++e) key[e] = gkeys[min(e * 64 + lane, n - 1)];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = e * 64 + lane;
+        if (i < n) {
+            const uint32_t d = (uint32_t)(key[e] >> 32);
+            dmin = min(dmin, d); dmax = max(dmax, d);
+        } else {
+            key[e] = ~0ull;
+        }
+        cnt[i] = 0u;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        dmin = min(dmin, (uint32_t)__shfl_xor((int)dmin, d, 64));
+        dmax = max(dmax, (uint32_t)__shfl_xor((int)dmax, d, 64));
+    }
+    wave_lds_fence();
+    const float fmin = __uint_as_float(dmin);                     // depths are positive floats: bit order == value order
+    const float scale = (float)(NB - 1) / fmaxf(__uint_as_float(dmax) - fmin, 1e-30f);
+    uint32_t bs[E];                                               // bucket | arrival slot in the bucket << 16
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        bs[e] = 0u;
+        if (e * 64 + lane < n) {
+            const float f = (__uint_as_float((uint32_t)(key[e] >> 32)) - fmin) * scale;
+            const uint32_t bkt = (uint32_t)min(NB - 1, (int)f);
+            bs[e] = bkt | (__hip_atomic_fetch_add(&cnt[bkt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) << 16);
+        }
+    }
+    wave_lds_fence();
+    // exclusive scan of the NB counters (lane l owns counters l * E .. l * E + E - 1) and the largest bucket
+    uint32_t c[E], sum = 0u, mx = 0u;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { c[e] = cnt[lane * E + e]; sum += c[e]; mx = max(mx, c[e]); }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+    if (mx > (uint32_t)BUCKET_MAX) {                              // wave-uniform; only the counters have been written
+        wave_rank_sort_staged<E>(key, n, sorted, keys_out, buf, lane);
+        return;
+    }
+    uint32_t run = incl - sum;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { cnt[lane * E + e] = run; run += c[e]; }      // counters -> bucket starts
+    wave_lds_fence();
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (e * 64 + lane < n) buf[cnt[bs[e] & 0xffffu] + (bs[e] >> 16)] = key[e];
+    wave_lds_fence();
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e * 64 + lane < n) {
+            const uint32_t bkt = bs[e] & 0xffffu;
+            const uint32_t s0 = cnt[bkt], s1 = bkt + 1u < (uint32_t)NB ? cnt[bkt + 1u] : (uint32_t)n;
+            uint32_t rank = s0;
+            for (uint32_t j = s0; j < s1; ++j) rank += buf[j] < key[e] ? 1u : 0u;
+            sorted[rank] = (uint32_t)key[e];
+            if (keys_out) keys_out[rank] = key[e];                // in place over the input: all keys sit in registers by now
+        }
     }
 }
 
@@ -494,6 +608,38 @@ __global__ __launch_bounds__(SBLOCK) void sort_short_kernel(Batch<RenderFwdArgs>
                          s_buf + wave * 64, lane);
 }
 
+// One list of more than MIN_N (>= 64) keys, sorted by the whole workgroup: the distribution sort, the merge sort for the
+// (rare) lists whose depths pile up in one bucket, the register rank sort beyond SORT_TILE.  n is workgroup-uniform.
+template <bool KEEP, int MIN_N>
+__device__ __forceinline__ void sort_list_workgroup(const RenderFwdArgs& a, int n, unsigned long long* gkeys, uint32_t* sorted,
+                                                    unsigned long long* s_buf, uint32_t* s_cnt, uint32_t* s_misc, int tid) {
+    unsigned long long* const keys_out = KEEP ? gkeys : nullptr;
+    if (n > SORT_TILE) {   // longer lists: 2048 own keys at a time against the whole list (any length)
+        for (int first = 0; first < n; first += 8 * SBLOCK) rank_sort_list<8>(gkeys, n, first, sorted, s_buf, tid);
+        if (keys_out) {    // the passes re-read the unsorted keys, so the sorted ones are rebuilt afterwards: depth bits of the record
+            __threadfence_block();
+            __syncthreads();
+            for (int i = tid; i < n; i += SBLOCK) {
+                const uint32_t id = sorted[i];
+                keys_out[i] = ((unsigned long long)__float_as_uint(a.splats[id].depth) << 32) | id;
+            }
+        }
+        return;
+    }
+    // distribution sort first; the merge sort takes the (rare) lists whose depths pile up in one bucket
+    bool done;
+    if (MIN_N < 256 && n <= 256) done = lds_bucket_sort<1>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
+    else if (MIN_N < 512 && n <= 512) done = lds_bucket_sort<2>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
+    else if (n <= 1024) done = lds_bucket_sort<4>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
+    else done = lds_bucket_sort<8>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
+    if (done) return;
+    __syncthreads();
+    if (MIN_N < 256 && n <= 256) lds_merge_sort<1>(gkeys, n, sorted, keys_out, s_buf, tid);   // (a plain O(n^2) rank sort of the whole
+    else if (MIN_N < 512 && n <= 512) lds_merge_sort<2>(gkeys, n, sorted, keys_out, s_buf, tid);    //  list was 40 % slower: LDS-pipe bound)
+    else if (n <= 1024) lds_merge_sort<4>(gkeys, n, sorted, keys_out, s_buf, tid);
+    else lds_merge_sort<8>(gkeys, n, sorted, keys_out, s_buf, tid);
+}
+
 // KEEP = true: merge source of a composite render (compose.hip): the sorted 64-bit keys replace the unsorted ones, in place.
 // Its own instantiation: as a run-time flag the extra stores cost the headline sort 1.4 us of 15.1 on C3.
 // Six waves per SIMD (<= 85 VGPRs; the eight-keys-per-thread paths of the long lists spill ~50 bytes): the launch is a
@@ -546,34 +692,86 @@ __global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         if (!SPLIT && tid < 64) wave_rank_sort64(gkeys, n, sorted, keys_out, s_buf, tid);      // (SPLIT: sort_short_kernel did it)
         return;
     }
-    if (n > SORT_TILE) {   // longer lists: 2048 own keys at a time against the whole list (any length)
-        for (int first = 0; first < n; first += 8 * SBLOCK) rank_sort_list<8>(gkeys, n, first, sorted, s_buf, tid);
-        if (keys_out) {    // the passes re-read the unsorted keys, so the sorted ones are rebuilt afterwards: depth bits of the record
-            __threadfence_block();
-            __syncthreads();
-            for (int i = tid; i < n; i += SBLOCK) {
-                const uint32_t id = sorted[i];
-                keys_out[i] = ((unsigned long long)__float_as_uint(a.splats[id].depth) << 32) | id;
-            }
-        }
-        return;
-    }
-    // distribution sort first; the merge sort takes the (rare) lists whose depths pile up in one bucket
-    bool done;
-    if (n <= 256) done = lds_bucket_sort<1>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
-    else if (n <= 512) done = lds_bucket_sort<2>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
-    else if (n <= 1024) done = lds_bucket_sort<4>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
-    else done = lds_bucket_sort<8>(gkeys, n, sorted, keys_out, s_buf, s_cnt, s_misc, tid);
-    if (done) return;
-    __syncthreads();
-    if (n <= 256) lds_merge_sort<1>(gkeys, n, sorted, keys_out, s_buf, tid);             // (a plain O(n^2) rank sort of the whole
-    else if (n <= 512) lds_merge_sort<2>(gkeys, n, sorted, keys_out, s_buf, tid);        //  list was 40 % slower: LDS-pipe bound)
-    else if (n <= 1024) lds_merge_sort<4>(gkeys, n, sorted, keys_out, s_buf, tid);
-    else lds_merge_sort<8>(gkeys, n, sorted, keys_out, s_buf, tid);
+    sort_list_workgroup<KEEP, 64>(a, n, gkeys, sorted, s_buf, s_cnt, s_misc, tid);
 #ifdef EXA_PROBE_SORT
     __syncthreads();
     if (tid == 0) a.tw.part_cnt[st] = (uint32_t)(__builtin_readcyclecounter() - t0);      // probe build only
 #endif
+}
+
+// The sort launch of images below SPLIT_SORT_SUBTILES sub-tiles (WAVE_KEYS > 0): ONE WAVE per list of up to WAVE_KEYS keys,
+// four lists per workgroup.  An avatar view has ~3 060 lists in 16 384 sub-tiles and 65 % (95 %) of them hold at most 256
+// (512) keys: with a 256-thread workgroup and 24 KiB of LDS per list, whatever its length, the launch above was bound by the
+// dispatch of its 16.4 k workgroups and by two rounds of residency, not by the ~1 us of sorting.  Grid, 256 threads each:
+//   [0, ORDER_WGS)     order_slots, as above
+//   `quads` workgroups wave w of quad q owns sub-tile 4 q + w in cell_desc order (the indexing of sort_short_kernel); quads
+//                      beyond the active cells leave after one scalar load.  n <= 64: wave_rank_sort64; n <= WAVE_KEYS:
+//                      wave_bucket_sort with the smallest E of {2, 4, 8} that fits; longer: not this wave's.  No barrier and no
+//                      loop over lists (a loop around the sorts spills: see above), each wave in its own quarter of the LDS.
+//   `tail` workgroups  one per WAVE_KEYS / 64 + 1 batch slots of the instance space: the one that finds the first such slot
+//                      of a list with n > WAVE_KEYS sorts it as the kernel above does; the others leave after one scalar
+//                      load.  No table, no counter, nothing the binning has to do for it.  (Built first: a table of
+//                      the long lists, appended by the sub-tile binning through one device atomic per cell.  Same sort
+//                      time, but the atomic's round trip cost subtile_bin 0.3 us: profiles/sort_wave_lists_ab.md.)
+// The same 24 640 bytes of static LDS and six waves per SIMD as the kernel above.
+template <bool KEEP>
+__global__ __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(6, 6))) void sort_subtiles_quads_kernel(Batch<RenderFwdArgs> batch,
+                                                                                                                int quads) {
+    constexpr int WK = WAVE_KEYS > 0 ? WAVE_KEYS : 256;           // (WAVE_KEYS = 0: never launched)
+    constexpr int TAIL_STRIDE = WK / BATCH + 1;                   // batch slots between the looks of two tail workgroups
+    static_assert(4 * WK * 12 <= SORT_TILE * 12, "four wave regions share the buffers of the workgroup sort");
+    __shared__ __attribute__((aligned(16))) unsigned long long s_buf[SORT_TILE + SORT_TILE / 2];     // keys | counters
+    __shared__ uint32_t s_misc[16];
+    uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_buf + SORT_TILE);
+    const RenderFwdArgs& a = batch.v[blockIdx.y];
+    const int tid = threadIdx.x;
+#ifdef EXA_PROBE_SORTLINE   // probe build only (tools/gpu_sort_timeline.py): start / end of every workgroup, 100 MHz clock
+    struct TL { const RenderFwdArgs& a; unsigned long long t0; int tid;
+        __device__ ~TL() { __syncthreads(); if (tid == 0) { a.tw.part_cnt[2 * blockIdx.x] = (uint32_t)t0; a.tw.part_cnt[2 * blockIdx.x + 1] = (uint32_t)wall_clock64(); } } } tl{a, (unsigned long long)wall_clock64(), tid};
+#endif
+    if (blockIdx.x < ORDER_WGS) {
+        static_assert(ORDER_LDS_WORDS <= SORT_TILE, "order_slots borrows the bucket counters of the sort");
+        order_slots(a.tw, a.store_ctx ? reinterpret_cast<uint32_t*>(a.bw.bucket) : nullptr, a.grid.subtiles, (int)blockIdx.x, tid,
+                    s_cnt, [&](int st) { return a.tw.ranges[st]; });
+        return;
+    }
+    const int q = (int)blockIdx.x - ORDER_WGS;
+    // (Measured and not taken: quads and tail workgroups ALTERNATING in the grid, so that the long lists -- dispatched behind
+    //  all the quads they start 4-8 us in -- start with the short ones: 10.4 -> 11.2 us at WAVE_KEYS 512, 11.8 at 256,
+    //  profiles/sort_wave_lists_ab.md.)
+    if (q < quads) {
+        if (q == 0 && tid == 0 && (uint64_t)a.tw.header->num_rendered > a.capacity) a.tw.header->overflow = 1u;
+        // (the first test also covers a job with a smaller image than the largest of the batch)
+        if (q * 4 >= a.grid.subtiles || q * 4 >= (int)a.tw.header->active_cells * SUBS_PER_CELL) return;
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        const int idx = q * 4 + wave;                               // the four lists of a quad lie in one cell
+        const int st = (int)a.tw.cell_desc[idx >> 6].x * SUBS_PER_CELL + (idx & 63);
+        const uint2 range = a.tw.ranges[st];
+        const int n = (int)(range.y - range.x);                     // wave-uniform; empty on overflow
+        if (n > 0 && n <= WK) {
+            unsigned long long* gkeys = a.bw.keys + range.x;
+            uint32_t* sorted = a.bw.sorted + range.x;
+            unsigned long long* const keys_out = KEEP ? gkeys : nullptr;
+            unsigned long long* const w_buf = s_buf + wave * (WK * 12 / 8);
+            uint32_t* const w_cnt = reinterpret_cast<uint32_t*>(w_buf + WK);
+            if (n <= 64) wave_rank_sort64(gkeys, n, sorted, keys_out, w_buf, lane);
+            else if (n <= 128) wave_bucket_sort<2>(gkeys, n, sorted, keys_out, w_buf, w_cnt, lane);
+            else if (WK == 256 || n <= 256) wave_bucket_sort<4>(gkeys, n, sorted, keys_out, w_buf, w_cnt, lane);
+            else wave_bucket_sort<WK / 64>(gkeys, n, sorted, keys_out, w_buf, w_cnt, lane);
+        }
+        return;
+    }
+    // Tail workgroup t looks at batch slot t * TAIL_STRIDE.  A list of more than WAVE_KEYS keys owns at least TAIL_STRIDE
+    // consecutive batch slots (common.h: ceil(n / 64) slots + an end slot, 64-aligned), so exactly one multiple of the stride
+    // is the FIRST one inside its slots: that workgroup sorts it.  The owner record {sub-tile + 1, begin, n} of the slot --
+    // the backward's work record, written by the sub-tile binning into a section cell_scatter_kernel zero-fills in every
+    // forward -- is the one load that says so: all-zero for unused and end slots and for an overflowed render.
+    const uint32_t slot = (uint32_t)(q - quads) * (uint32_t)TAIL_STRIDE;
+    if ((uint64_t)slot * BATCH >= a.capacity) return;               // (a job with a smaller buffer than the largest of the batch)
+    const uint4 own = a.bw.owner[slot];
+    const int n = (int)own.z;
+    if (own.x == 0u || n <= WK || slot - own.y / BATCH >= (uint32_t)TAIL_STRIDE) return;
+    sort_list_workgroup<KEEP, WK>(a, n, a.bw.keys + own.y, a.bw.sorted + own.y, s_buf, s_cnt, s_misc, tid);
 }
 
 // ---- blend ---------------------------------------------------------------------------------------------
@@ -799,6 +997,15 @@ hipError_t launch_sort_subtiles(const RenderFwdArgs* a, int K, hipStream_t s) {
         sort_short_kernel<<<dim3((subtiles + SBLOCK / 64 - 1) / (SBLOCK / 64), K), SBLOCK, 0, s>>>(make_batch(a, K));
         if (keep) sort_subtiles_kernel<true, true><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));
         else sort_subtiles_kernel<true, false><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));
+    } else if (WAVE_KEYS > 0) {
+        // tail: one workgroup per WAVE_KEYS / 64 + 1 batch slots of the largest buffer of the batch
+        const int quads = (subtiles + SBLOCK / 64 - 1) / (SBLOCK / 64);
+        int tail = 0;
+        for (int k = 0; k < K; ++k)
+            tail = max(tail, (int)((a[k].capacity / BATCH + WAVE_KEYS / BATCH) / (uint64_t)(WAVE_KEYS / BATCH + 1)));
+        const dim3 qgrid(ORDER_WGS + quads + tail, K);
+        if (keep) sort_subtiles_quads_kernel<true><<<qgrid, SBLOCK, 0, s>>>(make_batch(a, K), quads);
+        else sort_subtiles_quads_kernel<false><<<qgrid, SBLOCK, 0, s>>>(make_batch(a, K), quads);
     } else {
         if (keep) sort_subtiles_kernel<false, true><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));
         else sort_subtiles_kernel<false, false><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));

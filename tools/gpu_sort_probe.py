@@ -1,4 +1,5 @@
-"""Developer probe (needs a library built with -DEXA_PROBE_SORT): per-sub-tile cycles of the sort kernel."""
+"""Developer probe (needs a library built with -DEXA_PROBE_SORT -DEXA_WAVE_KEYS=0: the stamps are sort_subtiles_kernel's, one
+workgroup per sub-tile): per-sub-tile cycles of the sort kernel."""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, numpy as np

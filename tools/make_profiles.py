@@ -23,6 +23,7 @@ STAMP = 'library build %s (exavatar_release_amd.build._digest), sources at git %
 SHORT = {'zero_kernel': 'zero', 'preprocess_fwd_kernel': 'preprocess_fwd', 'col_scan_kernel': 'col_scan', 'cell_scan_kernel': 'cell_scan',
          'subtile_count_kernel': 'subtile_count',
          'cell_scatter_kernel': 'cell_scatter', 'subtile_bin_kernel': 'subtile_bin', 'sort_subtiles_kernel': 'sort_subtiles',
+         'sort_subtiles_quads_kernel': 'sort_subtiles',
          'render_fwd_kernel': 'render_fwd', 'render_bwd_kernel': 'render_bwd', 'preprocess_bwd_kernel': 'preprocess_bwd'}
 
 
