@@ -62,6 +62,12 @@ and for the scene side in front of the rasterizer (the body of ``SceneGaussian.f
 quaternion route and the SH colour seen from the camera centre, reference ``avatar/common/nets/module.py:253-272``):
 
     from exavatar_release_amd import scene_assets
+
+and for the per-frame pose parameters in front of the kinematics (``SMPLXParamDict``: 6D rotation parameters to axis-angle
+in one launch each way, and the detached pose features of ``HumanGaussian``, reference
+``avatar/common/nets/module.py:649-684,464,484,498``):
+
+    from exavatar_release_amd import SMPLXParamDict, pose_params, pose_features
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -81,6 +87,7 @@ from .kinematics import batch_rigid_transform, joint_transforms
 from .body import BodyOutput, BodyTemplate, MeshUpsampler
 from .vertex_regs import ArmPlan, ArmRGBReg, HandMeanReg, HandRGBReg, arm_neighbors, arm_rgb_loss, get_arm
 from .scene_assets import scene_assets
+from .pose_params import SMPLXParamDict, pose_features, pose_params
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -90,4 +97,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
-           'scene_assets']
+           'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features']

@@ -243,8 +243,9 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
             ExaRasterBackwardJob))
 
 # the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets, the forward
-# kinematics, the mesh upsampling and the SMPL-X template stage
-MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
+# kinematics with the pose parameters in front of them, the mesh upsampling, the SMPL-X template stage and the arm and
+# hand regularisers
+MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
     'exa_mesh_workspace_sizes': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ExaMeshWorkspaceSizes)]),
@@ -268,6 +269,10 @@ MESH = Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_kinematics_depths': (ctypes.c_int, [_I32, _IP, _IP]),
     'exa_mesh_kinematics_forward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 8),
     'exa_mesh_kinematics_backward': (ctypes.c_int, [_I32, _I32, _IP] + [c_void_p] * 11),
+    # the pose-parameter stage (csrc/pose_params.hip); `rows` and the arrays of device pointers are host arrays
+    'exa_mesh_pose_params_forward': (ctypes.c_int, [_I32, _IP, _PP, _PP, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_pose_params_backward': (ctypes.c_int, [_I32, _IP, _PP, _PP, c_void_p, _PP, c_void_p]),
+    'exa_mesh_pose_features': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 4),
     # the mesh upsampling and the SMPL-X template stage (csrc/body.hip); the plan's arrays are host int32 arrays
     'exa_mesh_upsample_plan': (ctypes.c_int, [_I32, _I32, _IP, _I32] + [_IP] * 7),
     'exa_mesh_upsample_forward': (ctypes.c_int, [_UP, _I32, c_void_p, c_void_p, c_void_p]),

@@ -57,6 +57,8 @@ SOURCES = {
     'vertex_regs.hip': ['-ffp-contract=off'],
     # the scene-Gaussian stage and its backward are defined operation by operation (include/exa_raster.h)
     'scene_assets.hip': ['-ffp-contract=off'],
+    # the pose-parameter stage and its backward are defined operation by operation (include/exa_mesh.h)
+    'pose_params.hip': ['-ffp-contract=off'],
 }
 
 

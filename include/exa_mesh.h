@@ -32,6 +32,10 @@
  * `ArmRGBReg`, `HandRGBReg` and `HandMeanReg` (avatar/common/nets/loss.py:148-197), under
  * `exavatar_release_amd.vertex_regs`.
  *
+ * And the pose parameters in front of the kinematics: `exa_mesh_pose_*` are the reference's `SMPLXParamDict.forward`
+ * (avatar/common/nets/module.py:649-684) and the detached pose features of module.py:464,484,498, under
+ * `exavatar_release_amd.pose_params`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -322,6 +326,78 @@ int exa_mesh_kinematics_backward(int32_t B, int32_t J, const int32_t* parents, c
                                  const float* joints, const float* pre, const float* grad_transforms,
                                  const float* grad_posed_joints, float* grad_pose, float* grad_rot, float* grad_joints,
                                  float* grad_pre, void* stream);
+
+/* ---- Pose parameters (reference SMPLXParamDict.forward) and the detached pose features -------------------------------
+ * `matrix_to_axis_angle(rotation_6d_to_matrix(p))` for the pose tensors of the frames of a call
+ * (avatar/common/nets/module.py:673-684), under `exavatar_release_amd.pose_params`: the per-frame 6D rotation parameters
+ * become the axis-angle rows the kinematics take, in ONE launch each way.  It joins this ABI like the kinematics it
+ * feeds; no existing prototype changes: EXA_MESH_VERSION stays 100.
+ *
+ * A call takes n_seg <= EXA_MESH_POSE_MAX_SEGMENTS segments: separately allocated [rows[s], 6] inputs (the parameters as
+ * they are; nothing is concatenated).  `rows`, and the arrays of pointers, are HOST arrays of n_seg entries whose
+ * pointers are device pointers; they are checked before any GPU work and travel to the kernel by value: no device
+ * buffer, no copy, no state between calls.  A segment of 0 rows is valid (its pointers are not read); n_seg == 0 and a
+ * call without rows are successful no-ops.  R = the sum of rows (<= EXA_MESH_POSE_MAX_ROWS); packed row start[s] + k is
+ * row k of segment s, start[s] = rows[0] + .. + rows[s - 1].  For one frame in the order root, body, jaw, leye, reye,
+ * lhand, rhand (1, 21, 1, 1, 1, 15, 15 rows) `packed` is the [55, 3] pose of exa_mesh_kinematics_forward.
+ *
+ * Forward, per row a = (a1, a2) of six floats; every operation rounded in fp32, no fused multiply-add, in this order
+ * (eps = 1e-12, F.normalize's):
+ *   1. rotation_6d_to_matrix:
+ *        n1 = sqrt((a1_0 a1_0 + a1_1 a1_1) + a1_2 a1_2);  d1 = max(n1, eps);  b1 = a1 / d1
+ *        dot = (b1_0 a2_0 + b1_1 a2_1) + b1_2 a2_2;  c = a2 - dot b1
+ *        n2, d2 of c likewise;  b2 = c / d2;  b3 = b1 x b2 = (b1_1 b2_2 - b1_2 b2_1, b1_2 b2_0 - b1_0 b2_2,
+ *        b1_0 b2_1 - b1_1 b2_0);  m = rows (b1, b2, b3)
+ *   2. matrix_to_quaternion:
+ *        x0 = ((1 + m00) + m11) + m22;  x1 = ((1 + m00) - m11) - m22;  x2 = ((1 - m00) + m11) - m22;
+ *        x3 = ((1 - m00) - m11) + m22;  i = the LOWEST index of the largest x;  q = sqrt(x_i);  qq = q q;  D = 2 q
+ *        A = m21 - m12, B = m02 - m20, C = m10 - m01, E = m10 + m01, F = m02 + m20, G = m12 + m21
+ *        row = (qq, A, B, C) | (A, qq, E, F) | (B, E, qq, G) | (C, F, G, qq) for i = 0 | 1 | 2 | 3
+ *        quat = row / D, negated as a whole when its first element is < 0.  (x_i >= 1, so neither the 0.1 floor nor
+ *        the positive part of pytorch3d's formula can bind.)  Steps 1 and 2 are exa_raster_scene_assets_forward's, bit
+ *        for bit; `quat` = (w, x, y, z) is written when asked for.
+ *   3. quaternion_to_axis_angle:
+ *        n = sqrt((x x + y y) + z z);  half = atan2(n, w);  angle = 2 half
+ *        s = sin(half) / angle, or 0.5 - (angle angle) / 48 when |angle| < 1e-6
+ *        out = (x / s, y / s, z / s)
+ *      atan2 and sin are the device library's atan2f / sinf: the steps a CPU does not reproduce bit for bit.
+ *
+ * Backward, atomic-free and bit-deterministic; everything is recomputed from the 6D row.  The row's cotangent g:
+ * grad_out[s]'s row when only that is given, grad_packed's when only that is, grad_out + grad_packed (one rounded
+ * addition) when both are, +0 when neither is.  torch's conventions: no gradient through the candidate index, the sign
+ * flip or the choice of the series; norm's gradient is 0 at 0; clamp_min passes the gradient where n >= eps.
+ *   T = (g_0 x + g_1 y) + g_2 z;  gs = -(T / (s s))
+ *   series:  g_angle = -(gs (angle / 24));           g_half = 2 g_angle
+ *   else:    g_angle = -(gs (s / angle));            g_half = 2 g_angle + (gs / angle) cos(half)      (cosf)
+ *   den = n n + w w;  gn = g_half (w / den);  gw = -(g_half (n / den));  k = gn / n, or 0 when n == 0
+ *   g_quat = (gw, g_0 / s + x k, g_1 / s + y k, g_2 / s + z k)
+ *   then the backward of steps 2 and 1 exactly as exa_raster_scene_assets_backward states it for the quaternion's
+ *   cotangent (exa_raster.h), giving the six floats of grad_d6's row.
+ * The identity row (1, 0, 0, 0, 1, 0) therefore gets the finite gradient (0, -1, 1, 0, 0, -1) for g = (1, 1, 1).
+ * Nothing is summed across rows: no workspace.
+ *
+ * exa_mesh_pose_features: from the kinematics' rot [J, 3, 3], the two detached features of module.py:464,484,498:
+ *   pose6d[6 j + k] = rot[1 + j] element k, k = 0 .. 5 (its first two rows: matrix_to_rotation_6d), j = 0 .. n_body - 1
+ *   pose_feat[9 j + k] = rot[1 + j] element k - (1 when k is 0, 4 or 8, else 0), j = 0 .. J - 2     (rot[1:] - I) */
+#define EXA_MESH_POSE_MAX_SEGMENTS 64
+#define EXA_MESH_POSE_MAX_ROWS (1 << 24)  /* R */
+
+/* One launch.  rows HOST int32 [n_seg]; d6 HOST [n_seg] of [dev] [rows[s], 6]; out HOST [n_seg] of [dev] [rows[s], 3],
+ * or NULL, and any entry may be NULL (not wanted); packed [dev] [R, 3] or NULL; quat [dev] [R, 4] or NULL.  What is
+ * given is fully written; with nothing wanted there is no launch. */
+int exa_mesh_pose_params_forward(int32_t n_seg, const int32_t* rows, const float* const* d6, float* const* out,
+                                 float* packed, float* quat, void* stream);
+
+/* One launch.  rows, d6 as in the forward; grad_out HOST [n_seg] of [dev] [rows[s], 3] or NULL, entries may be NULL;
+ * grad_packed [dev] [R, 3] or NULL; grad_d6 HOST [n_seg] of [dev] [rows[s], 6]: a NULL entry is a segment whose
+ * gradient is not wanted, and nothing is computed for it; the others are fully written.  All entries NULL: no launch. */
+int exa_mesh_pose_params_backward(int32_t n_seg, const int32_t* rows, const float* const* d6,
+                                  const float* const* grad_out, const float* grad_packed, float* const* grad_d6,
+                                  void* stream);
+
+/* One launch, forward only.  rot [dev] [J, 3, 3] (1 <= J <= EXA_MESH_KIN_MAX_JOINTS), 0 <= n_body <= J - 1;
+ * pose6d [dev] [6 n_body] and pose_feat [dev] [9 (J - 1)], either may be NULL. */
+int exa_mesh_pose_features(int32_t J, int32_t n_body, const float* rot, float* pose6d, float* pose_feat, void* stream);
 
 /* ---- Mesh upsampling (reference upsample_mesh: pytorch3d SubdivideMeshes.subdivide_homogeneous, once or twice) -----
  * One round appends, after the V vertices of a mesh, one vertex per unique edge, in ascending order of (low, high) (the
