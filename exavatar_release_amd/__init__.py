@@ -68,6 +68,11 @@ in one launch each way, and the detached pose features of ``HumanGaussian``, ref
 ``avatar/common/nets/module.py:649-684,464,484,498``):
 
     from exavatar_release_amd import SMPLXParamDict, pose_params, pose_features
+
+and for the posed SMPL-X layer behind them (``Model.get_smplx_outputs``: Rodrigues, the blend shapes, the pose correctives,
+the chain, the skinning and the camera -> world step in one call each way, reference ``avatar/main/model.py:37-58``):
+
+    from exavatar_release_amd import PosedBody
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -88,6 +93,7 @@ from .body import BodyOutput, BodyTemplate, MeshUpsampler
 from .vertex_regs import ArmPlan, ArmRGBReg, HandMeanReg, HandRGBReg, arm_neighbors, arm_rgb_loss, get_arm
 from .scene_assets import scene_assets
 from .pose_params import SMPLXParamDict, pose_features, pose_params
+from .posed_body import PosedBody, PosedBodyOutput
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -97,4 +103,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'skin_points', 'FusedMLP', 'LaplacianReg', 'mesh_laplacian_loss', 'BlendShapes', 'BlendTable',
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
-           'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features']
+           'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
+           'PosedBodyOutput']

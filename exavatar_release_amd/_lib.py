@@ -142,6 +142,16 @@ class ExaMeshBody(ctypes.Structure):
                 ('up', ctypes.POINTER(ExaMeshUpsample))]
 
 
+class ExaMeshPosed(ctypes.Structure):
+    """The tables of the posed SMPL-X stage (include/exa_mesh.h); `parents` is a host pointer."""
+    _fields_ = [('V', ctypes.c_int32), ('L', ctypes.c_int32), ('J', ctypes.c_int32), ('nnz', ctypes.c_int32),
+                ('parents', ctypes.POINTER(ctypes.c_int32)),
+                ('v_base', c_void_p), ('dirs', c_void_p), ('posedirs', c_void_p), ('pose_mean', c_void_p),
+                ('jreg_off', c_void_p), ('jreg_col', c_void_p), ('jreg_val', c_void_p),
+                ('jregT_off', c_void_p), ('jregT_row', c_void_p), ('jregT_val', c_void_p),
+                ('weights', c_void_p)]
+
+
 class ExaMlpNet(ctypes.Structure):
     """exa_mlp_net (include/exa_mlp.h): the arrays hold EXA_MLP_MAX_HEADS = 4 heads and EXA_MLP_MAX_LAYERS = 4 layers."""
     _fields_ = [('n_layers', ctypes.c_int32), ('in_width', ctypes.c_int32), ('shared_width', ctypes.c_int32),
@@ -190,6 +200,7 @@ _PP = ctypes.POINTER(c_void_p)       # host array of device pointers
 _IP = ctypes.POINTER(ctypes.c_int32)  # host array of int32
 _UP = ctypes.POINTER(ExaMeshUpsample)
 _BP = ctypes.POINTER(ExaMeshBody)
+_PBP = ctypes.POINTER(ExaMeshPosed)
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 
 # ---- the six ABIs
@@ -243,8 +254,8 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
             ExaRasterBackwardJob))
 
 # the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets, the forward
-# kinematics with the pose parameters in front of them, the mesh upsampling, the SMPL-X template stage and the arm and
-# hand regularisers
+# kinematics with the pose parameters in front of them, the mesh upsampling, the SMPL-X template stage, the posed SMPL-X
+# stage and the arm and hand regularisers
 MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_version': (ctypes.c_int, []),
     'exa_mesh_last_error': (ctypes.c_char_p, []),
@@ -281,6 +292,11 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_body_forward': (ctypes.c_int, [_BP, c_void_p, c_void_p, c_void_p, _U64] + [c_void_p] * 6),
     'exa_mesh_body_backward': (ctypes.c_int, [_BP, c_void_p, _U64] + [c_void_p] * 7 + [_U64, c_void_p, c_void_p,
                                                                                        c_void_p]),
+    # the posed SMPL-X stage (csrc/posed_body.hip)
+    'exa_mesh_posed_workspace_sizes': (ctypes.c_int, [_PBP, _U64P, _U64P]),
+    'exa_mesh_posed_forward': (ctypes.c_int, [_PBP, _I32] + [c_void_p] * 8 + [_U64] + [c_void_p] * 5),
+    'exa_mesh_posed_backward': (ctypes.c_int, [_PBP, _I32] + [c_void_p] * 3 + [_U64] + [c_void_p] * 4 + [_U64]
+                                + [c_void_p] * 6),
     # the arm and hand regularisers (csrc/vertex_regs.hip)
     'exa_mesh_arm_plan': (ctypes.c_int, [_I32, _I32, _I32, ctypes.c_float] + [c_void_p] * 11),
     'exa_mesh_arm_loss_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 7),
@@ -290,7 +306,8 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_hand_rgb_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 7),
     'exa_mesh_hand_mean_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 5),
     'exa_mesh_hand_mean_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 6),
-}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody))
+}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody,
+            ExaMeshPosed))
 
 # the K-nearest-neighbour search
 KNN = Abi('exa_knn', 'exa_knn.h', 100, {

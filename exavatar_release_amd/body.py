@@ -27,8 +27,8 @@ rotations over ``J``, gives ``joint_zero_pose``.  Every operation is rounded in 
 sum runs in an order that depends on the sizes and the tables alone, and no kernel uses an atomic: the same inputs give
 the same bits, forward and backward.
 
-Not covered: ``get_smplx_outputs`` (``avatar/main/model.py:37-58``), the third ``smplx_layer`` call, whose pose varies
-per frame; and the init-time ``get_neutral_pose_human(jaw_zero_pose=False, use_id_info=False)``, which runs once.  The
+``get_smplx_outputs`` (``avatar/main/model.py:37-58``), the third ``smplx_layer`` call, whose pose varies per frame, is
+``posed_body.PosedBody``.  Not covered: the init-time ``get_neutral_pose_human(jaw_zero_pose=False, use_id_info=False)``, which runs once.  The
 ``feat_list`` form of ``upsample_mesh`` runs at init only and stays with the stand-in.
 """
 import collections

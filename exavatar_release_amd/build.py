@@ -53,6 +53,8 @@ SOURCES = {
     'kinematics.hip': ['-ffp-contract=off'],
     # the mesh upsampling and the SMPL-X template stage are defined operation by operation (include/exa_mesh.h)
     'body.hip': ['-ffp-contract=off'],
+    # the posed SMPL-X stage and its backward are defined operation by operation (include/exa_mesh.h)
+    'posed_body.hip': ['-ffp-contract=off'],
     # the arm and hand regularisers are defined operation by operation (include/exa_mesh.h)
     'vertex_regs.hip': ['-ffp-contract=off'],
     # the scene-Gaussian stage and its backward are defined operation by operation (include/exa_raster.h)

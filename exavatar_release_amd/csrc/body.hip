@@ -27,6 +27,7 @@
 #include "../../include/exa_mesh.h"
 #include "../../include/exa_skin.h"
 #include "abi_status.h"
+#include "body.h"
 
 namespace exa_mesh_impl {
 
@@ -46,7 +47,7 @@ constexpr int BD_CROWS = 16;                  // direction rows per workgroup of
 constexpr int BD_MAXJ = EXA_MESH_KIN_MAX_JOINTS;
 constexpr int64_t BD_MAXV = EXA_MESH_BODY_MAX_VERTS;
 static_assert(BD_CHUNK == BD_BLOCK && BD_BLOCK == 4 * 64, "one element per lane, four waves per chunk");
-static_assert(BD_MAXL <= 2 * BD_BLOCK, "coef staging");
+static_assert(BD_MAXL <= BD_STAGE && 9 * (BD_MAXJ - 1) <= BD_STAGE, "coef staging");
 
 // ---- upsampling -----------------------------------------------------------------------------------------------------
 
@@ -196,22 +197,11 @@ void up_transpose(int32_t Vc, const std::vector<int32_t>& edges, int32_t* off, i
 
 // ---- the template stage ---------------------------------------------------------------------------------------------
 
-struct ShapeParams {
-    int32_t L, M;                             // M = 3 V
-    const float* coef;
-    const float* dirs;
-    const float* base;
-    const float* pose_offsets;                // NULL: v_posed is v_shaped
-    float* v_shaped;
-    float* v_posed;
-    float* zero3;
-};
-
 __global__ __launch_bounds__(BD_BLOCK) void body_shape(ShapeParams P) {
-    __shared__ float coef_l[BD_MAXL];
+    __shared__ float coef_l[BD_STAGE];
     const int tid = threadIdx.x;
-    for (int l = tid; l < P.L; l += BD_BLOCK) coef_l[l] = P.coef[l];
-    if (blockIdx.x == 0 && tid < 3) P.zero3[tid] = 0.0f;
+    for (int l = tid; l < P.L; l += BD_BLOCK) coef_l[l] = l < P.La ? P.coef[l] : P.coef_b[l - P.La];
+    if (blockIdx.x == 0 && tid < 3 && P.zero3) P.zero3[tid] = 0.0f;
     __syncthreads();
     const int m = blockIdx.x * BD_BLOCK + tid;
     if (m >= P.M) return;
@@ -236,16 +226,6 @@ __global__ __launch_bounds__(BD_BLOCK) void body_shape(ShapeParams P) {
     if (P.pose_offsets) P.v_posed[m] = vs + P.pose_offsets[m];
 }
 
-struct JregParams {
-    int32_t V, nnz, root;
-    const int32_t* off;
-    const int32_t* col;
-    const float* val;
-    const float* v_shaped;
-    const float* joint_offset;
-    float* Jr;
-};
-
 __global__ __launch_bounds__(64) void body_jreg(JregParams P) {
     const int j = blockIdx.x, lane = threadIdx.x;
     const int i0 = max(P.off[j], 0), i1 = min(P.off[j + 1], P.nnz);      // the guard: inside col / val
@@ -268,7 +248,7 @@ __global__ __launch_bounds__(64) void body_jreg(JregParams P) {
     }
     if (lane == 0) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) P.Jr[3 * j + c] = j == P.root ? p[c] : p[c] + P.joint_offset[3 * j + c];
+        for (int c = 0; c < 3; ++c) P.Jr[3 * j + c] = (j == P.root || !P.joint_offset) ? p[c] : p[c] + P.joint_offset[3 * j + c];
     }
 }
 
@@ -276,18 +256,6 @@ __global__ __launch_bounds__(BD_BLOCK) void body_add(int n, const float* a, cons
     const int i = blockIdx.x * BD_BLOCK + threadIdx.x;
     if (i < n) out[i] = a[i] + b[i];
 }
-
-struct JregBwdParams {
-    int32_t V, J, nnz, root;
-    const int32_t* off;                       // the transposed CSR
-    const int32_t* row;
-    const float* val;
-    const float* gJA;                         // [J, 3] or NULL
-    const float* gJC;                         // [J, 3] or NULL
-    const float* g_vp;                        // [V, 3] or NULL
-    float* d_joint_offset;                    // [J, 3] or NULL
-    float* dvs;                               // [V, 3] or NULL
-};
 
 __global__ __launch_bounds__(BD_BLOCK) void body_jreg_bwd(JregBwdParams P) {
     __shared__ float dJ[3 * BD_MAXJ];
@@ -313,14 +281,6 @@ __global__ __launch_bounds__(BD_BLOCK) void body_jreg_bwd(JregBwdParams P) {
     }
     P.dvs[m] = acc;
 }
-
-struct CoefParams {
-    int32_t L, M, chunks;
-    const float* dirs;
-    const float* dvs;
-    float* partial;                           // [chunks, L]
-    float* dcoef;
-};
 
 __global__ __launch_bounds__(BD_BLOCK) void body_coef_partial(CoefParams P) {
     __shared__ float wl[BD_CROWS][4];
@@ -349,7 +309,30 @@ __global__ __launch_bounds__(BD_BLOCK) void body_coef_finish(CoefParams P) {
     if (l >= P.L) return;
     float acc = 0.0f;
     for (int ch = 0; ch < P.chunks; ++ch) acc = acc + P.partial[(int64_t)ch * P.L + l];
-    P.dcoef[l] = acc;
+    if (l < P.split) P.dcoef[l] = acc;
+    else P.dcoef_b[l - P.split] = acc;
+}
+
+int launch_body_shape(const ShapeParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(body_shape, dim3(ceil_div(P.M, BD_BLOCK)), dim3(BD_BLOCK), 0, st, P);
+    return launched("body_shape");
+}
+
+int launch_body_jreg(const JregParams& P, int32_t J, hipStream_t st) {
+    hipLaunchKernelGGL(body_jreg, dim3(J), dim3(64), 0, st, P);
+    return launched("body_jreg");
+}
+
+int launch_body_jreg_bwd(const JregBwdParams& P, bool all_vertices, hipStream_t st) {
+    hipLaunchKernelGGL(body_jreg_bwd, dim3(all_vertices ? ceil_div(3 * (int64_t)P.V, BD_BLOCK) : 1), dim3(BD_BLOCK), 0, st, P);
+    return launched("body_jreg_bwd");
+}
+
+int launch_body_coef(const CoefParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(body_coef_partial, dim3(P.chunks, ceil_div(P.L, BD_CROWS)), dim3(BD_BLOCK), 0, st, P);
+    if (int rc = launched("body_coef_partial")) return rc;
+    hipLaunchKernelGGL(body_coef_finish, dim3(ceil_div(P.L, BD_BLOCK)), dim3(BD_BLOCK), 0, st, P);
+    return launched("body_coef_finish");
 }
 
 // the forward's workspace, in floats from its start (every section on a 256-byte boundary)
@@ -513,12 +496,11 @@ int exa_mesh_body_forward(const ExaMeshBody* body, const float* coef, const floa
     float* v_posed = b.pose_offsets ? ws + f.v_posed : v_shaped;
     const int M = 3 * b.V;
 
-    const ShapeParams S = {b.L, M, coef, b.dirs, b.v_base, b.pose_offsets, v_shaped, ws + f.v_posed, ws + f.zero3};
-    hipLaunchKernelGGL(body_shape, dim3(ceil_div(M, BD_BLOCK)), dim3(BD_BLOCK), 0, st, S);
-    if (int rc = launched("body_shape")) return rc;
+    const ShapeParams S = {b.L, M, b.L, coef, nullptr, b.dirs, b.v_base, b.pose_offsets, v_shaped, ws + f.v_posed,
+                           ws + f.zero3};
+    if (int rc = launch_body_shape(S, st)) return rc;
     const JregParams R = {b.V, b.nnz, b.root, b.jreg_off, b.jreg_col, b.jreg_val, v_shaped, joint_offset, ws + f.Jr};
-    hipLaunchKernelGGL(body_jreg, dim3(b.J), dim3(64), 0, st, R);
-    if (int rc = launched("body_jreg")) return rc;
+    if (int rc = launch_body_jreg(R, b.J, st)) return rc;
     if (int rc = exa_mesh_kinematics_forward(1, b.J, b.parents, nullptr, b.rot_pose, ws + f.Jr, nullptr, ws + f.A,
                                              joint_neutral_pose, ws + f.rot, stream))
         return rc;
@@ -614,15 +596,11 @@ int exa_mesh_body_backward(const ExaMeshBody* body, const void* fwd_ws, uint64_t
     const JregBwdParams Q = {b.V, b.J, b.nnz, b.root, b.jregT_off, b.jregT_row, b.jregT_val, gJA, gJC,
                              (have_mesh && dL_dcoef) ? at(w.gvp) : nullptr, dL_djoint_offset,
                              dL_dcoef ? at(w.dvs) : nullptr};
-    hipLaunchKernelGGL(body_jreg_bwd, dim3(dL_dcoef ? ceil_div(M, BD_BLOCK) : 1), dim3(BD_BLOCK), 0, st, Q);
-    if (int rc = launched("body_jreg_bwd")) return rc;
+    if (int rc = launch_body_jreg_bwd(Q, dL_dcoef != nullptr, st)) return rc;
     if (!dL_dcoef) return 0;
     const int chunks = (int)ceil_div(M, BD_CHUNK);
-    const CoefParams C = {b.L, M, chunks, b.dirs, at(w.dvs), at(w.partial), dL_dcoef};
-    hipLaunchKernelGGL(body_coef_partial, dim3(chunks, ceil_div(b.L, BD_CROWS)), dim3(BD_BLOCK), 0, st, C);
-    if (int rc = launched("body_coef_partial")) return rc;
-    hipLaunchKernelGGL(body_coef_finish, dim3(ceil_div(b.L, BD_BLOCK)), dim3(BD_BLOCK), 0, st, C);
-    return launched("body_coef_finish");
+    const CoefParams C = {b.L, M, chunks, b.L, b.dirs, at(w.dvs), at(w.partial), dL_dcoef, nullptr};
+    return launch_body_coef(C, st);
 }
 
 }  // extern "C"

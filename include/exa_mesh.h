@@ -536,6 +536,99 @@ int exa_mesh_body_backward(const ExaMeshBody* body, const void* fwd_ws, uint64_t
                            const float* g_joint_zero_pose, void* bwd_ws, uint64_t bwd_ws_bytes, float* dL_dcoef,
                            float* dL_djoint_offset, void* stream);
 
+/* ---- Posed SMPL-X stage (reference Model.get_smplx_outputs, avatar/main/model.py:37-58) -----------------------------
+ * The `smplx_layer` call whose pose varies per frame, one sample per call: smplx's `batch_rodrigues`, the two blend-shape
+ * sums, the pose correctives, `batch_rigid_transform`, the dense skinning, `+ transl` and the camera -> world step, as
+ * one C call each way.  V vertices, L = Lb + Le coefficients (1 <= L <= EXA_MESH_BODY_MAX_COEF; betas [Lb] and
+ * expression [Le] are two pointers, either may be empty), 1 <= J <= EXA_MESH_KIN_MAX_JOINTS, P = 9 (J - 1) pose features.
+ * It joins this ABI like the template stage whose launches it shares; no existing prototype changes: EXA_MESH_VERSION
+ * stays 100.  Every operation is rounded in fp32 and never contracted; every sum runs in an order that depends on the
+ * sizes and the tables alone.  With m = 3 v + c and I the identity:
+ *   1. f = pose[j] + pose_mean[j]  (f = pose[j] without a pose_mean);  e = f + 1e-8f  (per component)
+ *   2. a = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2);  d = f / a;  s = sin(a), c = cos(a)  (the device library's sinf / cosf:
+ *      the one step a CPU does not reproduce bit for bit; both are kept for the backward);  q = 1 - c
+ *      K = [0, -d_2, d_1;  d_2, 0, -d_0;  -d_1, d_0, 0];   KK[r][k] = (K[r][0] K[0][k] + K[r][1] K[1][k]) + K[r][2] K[2][k]
+ *      rot[j][r][k] = (I[r][k] + s K[r][k]) + q KK[r][k]                   (smplx lbs.py:311-345, not pytorch3d's route)
+ *   3. v_shaped[m] = v_base[m] + S,  S = +0.0, then for l = 0 .. L-1 in order S = S + coef[l] * dirs[l][m], coef[l] =
+ *      betas[l] for l < Lb and expression[l - Lb] for the others  (v_base = v_template + face_offset, added once by the
+ *      caller; dirs is feature-major [L, 3 V])
+ *   4. Jr[j][c] = the template stage's regressor sum over v_shaped (lanes, then the tree) + joint_offset[j][c], for EVERY
+ *      joint, the root included (model.py:50 passes the parameter as it is); without a joint_offset nothing is added
+ *   5. feat[9 (j - 1) + 3 r + k] = rot[j][r][k] - I[r][k]                  j = 1 .. J-1
+ *   6. v_posed[m] = v_shaped[m] + C,  C = +0.0, then for p = 0 .. P-1 in order C = C + feat[p] * posedirs[p][m]
+ *      (posedirs [P, 3 V] in the layer's own layout; J == 1: v_posed = v_shaped)
+ *   7. chain = exa_mesh_kinematics_forward(rot_in = rot, joints = Jr): posed joints, A
+ *   8, 9. vertices = exa_skin_forward(points = v_posed, T = A, weights, no idx, trans = transl, no camera step)
+ *   10. joints[j][c] = posed_joints[j][c] + transl[c]
+ *   11. with Rinv and t: d = vertices[v] - t;  vertices_world[v][r] = (Rinv[r][0] d_0 + Rinv[r][1] d_1) + Rinv[r][2] d_2
+ * Seven launches (six for J == 1): posed_rodrigues, body_shape, body_jreg, body_shape over posedirs, kin_fwd, skin_fwd,
+ * posed_finish.
+ *
+ * Backward, at most ten launches, no atomics.  Any of the three cotangents may be NULL (none); a step nothing reaches,
+ * or that only unwanted gradients need, is not launched.
+ *   gv[v][c] = g_vertices[v][c] + ((Rinv[0][c] g_0 + Rinv[1][c] g_1) + Rinv[2][c] g_2),  g = g_vertices_world[v]  (one of
+ *              them alone where the other is missing)
+ *   exa_skin_backward(points = v_posed, grad_out = gv): grad_points = g_vp, grad_T = g_A, grad_trans = g_tr
+ *   exa_mesh_kinematics_backward(chain; grad_transforms = g_A, grad_posed_joints = g_joints): grad_rot = g_R,
+ *              grad_joints = g_J
+ *   dL_djoint_offset = g_J  (+0.0 where nothing reaches the chain)
+ *   dvs[v][c] = g_vp[v][c] (+0.0 without gv), then the regressor's transpose over g_J as in the template stage
+ *   dL_dbetas, dL_dexpression: the template stage's two-level sum of dirs[l][m] * dvs[m] over chunks of
+ *              EXA_MESH_BODY_CHUNK, for the rows of the wanted tensors only
+ *   g_feat[p] = the same two-level sum of posedirs[p][m] * g_vp[m]: the correctives' transpose, 3 V terms per feature
+ *   G = g_R[j] + g_feat[9 (j - 1) ..] (one alone where the other is missing or j == 0, +0.0 without both), then with s, c
+ *   of the forward and f, e, a, d, K, KK recomputed as above:
+ *       g_s = +0.0, then for k = 0 .. 8 (row-major) in order g_s = g_s + G[k] K[k];   g_q likewise over KK
+ *       X[r][k] = (G[r][0] K[k][0] + G[r][1] K[k][1]) + G[r][2] K[k][2];   Y[r][k] = (K[0][r] G[0][k] + K[1][r] G[1][k]) +
+ *       K[2][r] G[2][k];   g_K[r][k] = s G[r][k] + q (X[r][k] + Y[r][k])
+ *       g_d = (g_K[2][1] - g_K[1][2],  g_K[0][2] - g_K[2][0],  g_K[1][0] - g_K[0][1])
+ *       g_a = (g_s c + g_q s) - ((g_d0 d_0 + g_d1 d_1) + g_d2 d_2) / a
+ *       dL_dpose[j][k] = g_d[k] / a + g_a (e_k / a)
+ *   The 1e-8 keeps a > 0 at a zero row, whose gradient is therefore finite.
+ *   dL_dtransl[c] = g_tr[c] + T,  T = +0.0, then for j = 0 .. J-1 in order T = T + g_joints[j][c]  (one alone where the
+ *              other is missing)
+ * The forward's workspace holds what the backward reads (sin / cos, rot, v_posed, Jr, A) and must stay untouched until
+ * then; its first 2 J floats are (sin a_j, cos a_j).  pose_mean, face_offset and the camera get no gradient. */
+typedef struct ExaMeshPosed {
+    int32_t V, L, J;                    /* vertices, coefficients (Lb + Le), joints */
+    int32_t nnz;                        /* non-zeros of the joint regressor, 0 .. J V */
+    const int32_t* parents;             /* HOST [J]: the tree, as exa_mesh_kinematics_* take it */
+    const float* v_base;                /* [dev] [V, 3] */
+    const float* dirs;                  /* [dev] [L, 3 V] feature-major */
+    const float* posedirs;              /* [dev] [9 (J - 1), 3 V]; unused with J == 1 */
+    const float* pose_mean;             /* [dev] [J, 3] or NULL */
+    const int32_t* jreg_off;            /* [dev] [J + 1]; the six regressor arrays as in ExaMeshBody */
+    const int32_t* jreg_col;            /* [dev] [nnz] */
+    const float* jreg_val;              /* [dev] [nnz] */
+    const int32_t* jregT_off;           /* [dev] [V + 1] */
+    const int32_t* jregT_row;           /* [dev] [nnz] */
+    const float* jregT_val;             /* [dev] [nnz] */
+    const float* weights;               /* [dev] [V, J] skinning weights */
+} ExaMeshPosed;
+
+/* Host only: the bytes of the forward's and the backward's workspace, from V, L and J alone. */
+int exa_mesh_posed_workspace_sizes(const ExaMeshPosed* posed, uint64_t* fwd_bytes, uint64_t* bwd_bytes);
+
+/* posed HOST pointer; 0 <= Lb <= L; pose [dev] [J, 3]; betas [dev] [Lb] and expression [dev] [L - Lb] (NULL where
+ * empty); transl [dev] [3]; joint_offset [dev] [J, 3] or NULL; Rinv [dev] [3, 3] and t [dev] [3], both or neither; fwd_ws
+ * [dev] of fwd_ws_bytes >= fwd_bytes.  Outputs, each [dev], fully written: vertices [V, 3], joints [J, 3], rot [J, 3, 3]
+ * (required) and vertices_world [V, 3] (given exactly when Rinv is).  Everything is validated on the host before any
+ * GPU work. */
+int exa_mesh_posed_forward(const ExaMeshPosed* posed, int32_t Lb, const float* pose, const float* betas,
+                           const float* expression, const float* transl, const float* joint_offset, const float* Rinv,
+                           const float* t, void* fwd_ws, uint64_t fwd_ws_bytes, float* vertices, float* joints,
+                           float* vertices_world, float* rot, void* stream);
+
+/* pose, Rinv, fwd_ws: the forward's.  g_* [dev], shaped as the outputs, each may be NULL.  bwd_ws [dev] of bwd_ws_bytes
+ * >= bwd_bytes.  dL_dpose [J, 3], dL_dbetas [Lb], dL_dexpression [L - Lb], dL_dtransl [3], dL_djoint_offset [J, 3]: each
+ * [dev], each may be NULL (not wanted: the steps only it needs are not launched), fully written when given.  With none
+ * wanted there is no launch. */
+int exa_mesh_posed_backward(const ExaMeshPosed* posed, int32_t Lb, const float* pose, const float* Rinv,
+                            const void* fwd_ws, uint64_t fwd_ws_bytes, const float* g_vertices, const float* g_joints,
+                            const float* g_vertices_world, void* bwd_ws, uint64_t bwd_ws_bytes, float* dL_dpose,
+                            float* dL_dbetas, float* dL_dexpression, float* dL_dtransl, float* dL_djoint_offset,
+                            void* stream);
+
 /* ---- Arm and hand regularisers (reference ArmRGBReg, HandRGBReg, HandMeanReg, loss.py:148-197) -----------------------
  * Three more per-vertex losses of the upsampled mesh, V vertices, B batch elements, three channels.  Every operation
  * is rounded in fp32 and never contracted; every sum runs in the order stated here.  No atomics, no memset: every
