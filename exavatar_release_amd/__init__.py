@@ -73,6 +73,11 @@ and for the posed SMPL-X layer behind them (``Model.get_smplx_outputs``: Rodrigu
 the chain, the skinning and the camera -> world step in one call each way, reference ``avatar/main/model.py:37-58``):
 
     from exavatar_release_amd import PosedBody
+
+and for the face composite in front of ``rgb_face`` / ``rgb_face_refined`` and the overlays of the test branch (reference
+``avatar/main/model.py:200-201, 207-208, 268-276``):
+
+    from exavatar_release_amd import FaceRGBLoss, face_composite, foreground_composite
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -94,6 +99,7 @@ from .vertex_regs import ArmPlan, ArmRGBReg, HandMeanReg, HandRGBReg, arm_neighb
 from .scene_assets import scene_assets
 from .pose_params import SMPLXParamDict, pose_features, pose_params
 from .posed_body import PosedBody, PosedBodyOutput
+from .face_loss import FaceRGBLoss, face_composite, foreground_composite
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -104,4 +110,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
-           'PosedBodyOutput']
+           'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite']

@@ -166,6 +166,7 @@ STORE_CTX, STAGE_NO_BLEND, STAGE_BLEND_ONLY, STAGE_NO_SORT, STAGE_SORT_ONLY = 1,
 
 TIMING_SLOTS = 9
 KNN_NO_CULL = 1      # EXA_KNN_NO_CULL
+COMPOSITE_FACE_HARD, COMPOSITE_FACE_SOFT, COMPOSITE_FOREGROUND = 0, 1, 2      # EXA_COMPOSITE_*
 
 
 class Abi:
@@ -247,6 +248,14 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
                             [ctypes.c_float, ctypes.c_float] + [c_void_p] * 3),
     'exa_l1_forward': (ctypes.c_int, [_I32] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [c_void_p] * 6),
     'exa_l1_backward': (ctypes.c_int, [_I32] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [c_void_p] * 7),
+    # the face-composited L1 term and the composites (csrc/face_loss.hip)
+    'exa_face_l1_blocks': (ctypes.c_int64, [_I32, _I32, _I32, _I32]),
+    'exa_face_l1_forward': (ctypes.c_int, [_I32] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [c_void_p] * 6),
+    'exa_face_l1_reduce': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [c_void_p] * 3),
+    'exa_face_l1_backward': (ctypes.c_int, [_I32] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [c_void_p] * 5 +
+                             [ctypes.c_int64] + [c_void_p] * 3),
+    'exa_composite_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 4 + [ctypes.c_float, c_void_p]),
+    'exa_composite_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 6),
     'exa_raster_timing_enable': (ctypes.c_int, [_I32]),
     'exa_raster_timing_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _I32]),
     'exa_raster_timing_name': (ctypes.c_char_p, [_I32]),

@@ -61,6 +61,8 @@ SOURCES = {
     'scene_assets.hip': ['-ffp-contract=off'],
     # the pose-parameter stage and its backward are defined operation by operation (include/exa_mesh.h)
     'pose_params.hip': ['-ffp-contract=off'],
+    # the face-composited L1 term and the composites are defined operation by operation (include/exa_raster.h)
+    'face_loss.hip': ['-ffp-contract=off'],
 }
 
 

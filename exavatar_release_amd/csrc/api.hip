@@ -780,6 +780,79 @@ int exa_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* c
     return 0;
 }
 
+// the one-dimensional grids of face_loss.hip index their runs of 4 pixels with 32 bits
+static int check_face_runs(int32_t B, int32_t H, int32_t W) {
+    if ((int64_t)B * H * ((W + 3) / 4 + 1) > 0x7fffffffLL)
+        return fail(EXA_RASTER_E_INVALID, "face loss: more than 2^31 - 1 runs of 4 pixels");
+    return 0;
+}
+
+int64_t exa_face_l1_blocks(int32_t B, int32_t C, int32_t crop_w, int32_t crop_h) {
+    if (B < 0 || C <= 0 || crop_w < 0 || crop_h < 0) return 0;
+    return face_l1_blocks(B, crop_w, crop_h);
+}
+
+int exa_face_l1_forward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                        const float* face, const float* img_target, float* l1_map, float* partials, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((rc = check_face_runs(B, H, W))) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !face || !img_target))
+        return fail(EXA_RASTER_E_NULLPTR, "face_l1: NULL argument");
+    EXA_HIP(launch_face_l1_fwd(B, C, H, W, crop, img_out, face, img_target, l1_map, partials,
+                               static_cast<hipStream_t>(stream)), "face_l1_fwd");
+    return 0;
+}
+
+int exa_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out_mean, void* stream) {
+    if (n_partials < 0 || n_elements < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (!out_mean || (n_partials > 0 && !partials)) return fail(EXA_RASTER_E_NULLPTR, "face_l1 reduce: NULL argument");
+    EXA_HIP(launch_face_l1_reduce(n_partials, n_elements, partials, out_mean, static_cast<hipStream_t>(stream)),
+            "face_l1_reduce");
+    return 0;
+}
+
+int exa_face_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                         const float* face, const float* img_target, const float* dL_dmap, const float* dL_dmean,
+                         int64_t n_elements, float* dL_dimg, float* dL_dface, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((rc = check_face_runs(B, H, W))) return rc;
+    if ((dL_dmap != nullptr) == (dL_dmean != nullptr))
+        return fail(EXA_RASTER_E_INVALID, "face_l1 backward: pass exactly one of dL_dmap / dL_dmean");
+    if (dL_dmean && n_elements < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if ((int64_t)B * crop[2] * crop[3] > 0 && (dL_dimg || dL_dface) && (!img_out || !face || !img_target))
+        return fail(EXA_RASTER_E_NULLPTR, "face_l1: NULL argument");
+    EXA_HIP(launch_face_bwd(1, B, C, H, W, crop, img_out, face, img_target, dL_dmap, dL_dmean, n_elements, dL_dimg,
+                            dL_dface, static_cast<hipStream_t>(stream)), "face_l1_bwd");
+    return 0;
+}
+
+int exa_composite_forward(int32_t mode, int32_t B, int32_t C, int32_t H, int32_t W, const float* a, const float* sel,
+                          const float* b, float* out, float thr, void* stream) {
+    if (mode != EXA_COMPOSITE_FACE_HARD && mode != EXA_COMPOSITE_FACE_SOFT && mode != EXA_COMPOSITE_FOREGROUND)
+        return fail(EXA_RASTER_E_INVALID, "composite: unknown mode");
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (int rc = check_face_runs(B, H, W)) return rc;
+    if ((int64_t)B * C * H * W > 0 && (!sel || !b || !out || (mode == EXA_COMPOSITE_FOREGROUND && !a)))
+        return fail(EXA_RASTER_E_NULLPTR, "composite: NULL argument");
+    EXA_HIP(launch_composite_fwd(mode, B, C, H, W, a, sel, b, out, thr, static_cast<hipStream_t>(stream)), "composite_fwd");
+    return 0;
+}
+
+int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const float* img, const float* face,
+                           const float* dL_dout, float* dL_dimg, float* dL_dface, void* stream) {
+    (void)img;                                             // the selection is decided by the face render alone
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (int rc = check_face_runs(B, H, W)) return rc;
+    if ((int64_t)B * H * W > 0 && (dL_dimg || dL_dface) && (!face || !dL_dout))
+        return fail(EXA_RASTER_E_NULLPTR, "composite: NULL argument");
+    const int32_t crop[4] = {0, 0, W, H};
+    EXA_HIP(launch_face_bwd(0, B, C, H, W, crop, nullptr, face, nullptr, dL_dout, nullptr, 0, dL_dimg, dL_dface,
+                            static_cast<hipStream_t>(stream)), "composite_bwd");
+    return 0;
+}
+
 int exa_raster_timing_enable(int32_t on) {
     if (on && !g_t.created) {
         for (int i = 0; i < K_COUNT; ++i)

@@ -578,5 +578,18 @@ hipError_t launch_scene_assets_bwd(int P, int Mr, int deg, const float* mean, co
                                    const float* scale_out, const float* g_opacity_out, const float* g_scale_out,
                                    const float* g_rotation_out, const float* g_rgb, float* g_mean, float* g_opacity,
                                    float* g_scale, float* g_rotation, float* g_dc, float* g_rest, hipStream_t s);
+// face_loss.hip: the face-composited L1 term and the composites (sizes, the window and the pointers are the caller's to
+// check).  face_l1_blocks: the workgroups (= partial sums) of the forward; face_image_blocks: those of a full-image walk.
+int64_t face_l1_blocks(int B, int cw, int ch);
+int64_t face_image_blocks(int B, int H, int W);
+hipError_t launch_face_l1_fwd(int B, int C, int H, int W, const int* crop, const float* img, const float* face,
+                              const float* tgt, float* map, float* partials, hipStream_t s);
+hipError_t launch_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out, hipStream_t s);
+// l1 != 0: the L1 term's backward (one of g_map / g_mean); l1 == 0: the hard composite's (g_map = dL_dout, crop = the image)
+hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, const float* img, const float* face,
+                           const float* tgt, const float* g_map, const float* g_mean, int64_t n_elements, float* d_img,
+                           float* d_face, hipStream_t s);
+hipError_t launch_composite_fwd(int mode, int B, int C, int H, int W, const float* a, const float* sel, const float* b,
+                                float* out, float thr, hipStream_t s);
 
 }  // namespace exa

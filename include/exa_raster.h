@@ -485,6 +485,73 @@ int exa_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* c
                     void* stream);
 
 /*
+ * The face composite in front of the L1 term and the composites of the test branch (csrc/face_loss.hip): reference
+ * avatar/main/model.py:200-201, 207-208 (`is_face = ((face[:, :3] != -1) * (face[:, 3:] == 1)).float()`,
+ * `rgb_loss(img * (1 - is_face) + face[:, :3] * is_face, target, bbox)`) and model.py:268-276.
+ * img_out, img_target: [B, C, H, W]; face: [B, C + 1, H, W], C colour planes and one coverage plane (the face render of
+ * exa_mesh_forward: -1 in every channel of a background pixel); crop = {x0, y0, w, h}, the clamped bbox, as for
+ * exa_l1_forward.  All arithmetic is fp32, one rounding per operation written, no fused multiply-adds.
+ *
+ * Work split of every kernel: one thread owns one RUN, the 4 consecutive pixels x = 4 q .. 4 q + 3 of one image row (q counts
+ * from the image's left edge), reads the coverage plane once and walks the C colour planes.  A run wholly inside the
+ * window moves with 16-byte loads and stores when W is a multiple of 4 and the arrays are 16-byte aligned (the window-shaped
+ * arrays l1_map / dL_dmap: when x0 and w are multiples of 4 as well); every other pixel moves by itself.  Workgroups of
+ * 256 threads on a one-dimensional grid; thread index i = (b * rows + row) * runs + run.  No atomics anywhere.
+ *
+ * exa_face_l1_forward: rows = h, runs = (w + 6) / 4 (the runs a window of w pixels can touch, wherever it starts; run r of
+ *   a window row is q = x0 / 4 + r, and a last run behind the window holds nothing), grid = exa_face_l1_blocks().
+ *   Per window pixel and channel c:  f = (face_c != -1) && (coverage == 1);  v = f ? face_c : img_out_c;
+ *   t = |v - img_target_c|.  l1_map ([B, C, h, w], or NULL) receives t.  partials (or NULL) receives one float per
+ *   workgroup, the sum of the workgroup's t in this order:
+ *     thread:     s = 0; for c = 0 .. C - 1: for k = 0 .. 3: if pixel 4 q + k is in the window: s = s + t   (4 C additions)
+ *     wave:       for distance = 32, 16, 8, 4, 2, 1: s = s + s[lane ^ distance]                              (6 additions)
+ *     workgroup:  ((wave 0 + wave 1) + wave 2) + wave 3                                                      (3 additions)
+ *   Threads without a run or a window pixel enter with s = 0.
+ * exa_face_l1_blocks: the number of partials, ceil(B * h * ((w + 6) / 4) / 256); 0 for an empty window, B or C.
+ * exa_face_l1_reduce: ONE workgroup of 256 threads.  Thread j adds partials j, j + 256, j + 512, .. in that order to
+ *   s = 0 (ceil(n_partials / 256) additions), then the wave and workgroup sums above (9 additions), and thread 0 writes
+ *   out_mean = sum / (float)n_elements (n_elements = 0: NaN, as torch.mean of an empty map).  The mean is therefore two
+ *   launches and the same bits on every call; an element passes through at most
+ *   4 C + 9 + ceil(n_partials / 256) + 9 additions.
+ * exa_face_l1_backward: rows = H, runs = ceil(W / 4): the launch walks the whole image.  Exactly one of dL_dmap
+ *   ([B, C, h, w]) and dL_dmean is non-NULL; dL_dmean is a DEVICE pointer to one float, read on the device as
+ *   g = *dL_dmean * (1 / (float)n_elements), the quotient rounded and then the product (no host read-back).  That is what
+ *   torch's backward of .mean() leaves on the device -- its division of a device tensor by a host scalar multiplies by the
+ *   rounded reciprocal -- and can differ from *dL_dmean / (float)n_elements, which torch forms on the CPU, in the last bit.
+ *   Per window pixel and channel, with g the cotangent,
+ *   d = v - img_target_c and s = (d > 0 ? 1 : 0) - (d < 0 ? 1 : 0):
+ *     dL_dimg_c = f ? 0 : s * g;    dL_dface_c = f ? s * g : 0.
+ *   dL_dimg [B, C, H, W] and dL_dface [B, C + 1, H, W] may each be NULL; each one given is written WHOLE: zeros outside
+ *   the window and in the coverage plane of dL_dface (the reference's `== 1` cuts that gradient).  The caller clears
+ *   nothing.  Only window pixels read img_out, face, img_target and dL_dmap.
+ * exa_composite_forward: the full image, rows = H, runs = ceil(W / 4); out [B, C, H, W]:
+ *   EXA_COMPOSITE_FACE_HARD   sel = face [B, C + 1, H, W]:  out_c = f ? face_c : b_c  (a is not read and may be NULL)
+ *   EXA_COMPOSITE_FACE_SOFT   sel = face:  w = (face_c != -1 ? 1 : 0) * coverage;  out_c = b_c * (1 - w) + face_c * w, the two
+ *                             products rounded before the sum (model.py:268-271; a is not read)
+ *   EXA_COMPOSITE_FOREGROUND  sel = mask [B, 1, H, W]:  out_c = mask > thr ? a_c : b_c  (model.py:273-276; the reference's
+ *                             is_fg * a + (1 - is_fg) * b with a 0 / 1 weight is this selection for finite inputs)
+ * exa_composite_backward: EXA_COMPOSITE_FACE_HARD only: dL_dimg_c = f ? 0 : dL_dout_c, dL_dface_c = f ? dL_dout_c : 0, the
+ *   coverage plane of dL_dface zero; either output may be NULL; img is not read (the selection is the face render's alone)
+ *   and may be NULL.
+ * Negative sizes, a window outside the image, both or neither cotangent, an unknown mode: EXA_RASTER_E_INVALID; a missing
+ * array: EXA_RASTER_E_NULLPTR; both before any device call.  The calls neither allocate nor synchronise.
+ */
+#define EXA_COMPOSITE_FACE_HARD 0
+#define EXA_COMPOSITE_FACE_SOFT 1
+#define EXA_COMPOSITE_FOREGROUND 2
+int64_t exa_face_l1_blocks(int32_t B, int32_t C, int32_t crop_w, int32_t crop_h);
+int exa_face_l1_forward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                        const float* face, const float* img_target, float* l1_map, float* partials, void* stream);
+int exa_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out_mean, void* stream);
+int exa_face_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                         const float* face, const float* img_target, const float* dL_dmap, const float* dL_dmean,
+                         int64_t n_elements, float* dL_dimg, float* dL_dface, void* stream);
+int exa_composite_forward(int32_t mode, int32_t B, int32_t C, int32_t H, int32_t W, const float* a, const float* sel,
+                          const float* b, float* out, float thr, void* stream);
+int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const float* img, const float* face,
+                           const float* dL_dout, float* dL_dimg, float* dL_dface, void* stream);
+
+/*
  * Optional per-kernel timing for benchmarks (the only state the library ever keeps, process-wide,
  * off by default, not thread-safe).  While enabled, every kernel / memset the library enqueues is bracketed by a
  * pair of hipEvents recorded on the caller's stream.  exa_raster_timing_read() synchronises on the
