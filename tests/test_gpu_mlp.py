@@ -5,27 +5,17 @@ must not depend on N or on its position; repeated calls and graph replays must g
 reference's size the result must agree with PyTorch's fp32 nn.Sequential + autograd within a stated bound."""
 import copy
 
-import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
+import mlp_cases as mc
 import mlp_oracle as mo
+from mlp_cases import bits_equal, params_of, trunk, zero_grads
 
 pytestmark = pytest.mark.gpu
 
 TRI, POSE, NORMAL = 96, 126, 3          # triplane feature (3 x 32), body pose 6d (21 x 6), normal
-
-
-def trunk(widths, trailing=0, groups=4):
-    """nn.Sequential of Linear -> GroupNorm(groups, 128) -> ReLU layers over ``widths``, then a plain Linear(128,
-    trailing) when ``trailing`` (the structure make_linear_layers(..., use_gn=True) builds)."""
-    mods = []
-    for a, b in zip(widths[:-1], widths[1:]):
-        mods += [nn.Linear(a, b), nn.GroupNorm(groups, b), nn.ReLU(inplace=True)]
-    if trailing:
-        mods.append(nn.Linear(widths[-1], trailing))
-    return nn.Sequential(*mods)
 
 
 def reference_nets(seed=0):
@@ -70,95 +60,15 @@ def unfolded(blocks):
     return tuple('pose_rows' if b == 'pose' else b for b in blocks)
 
 
-def oracle_net(fm, blocks):
-    """The oracle's net for a FusedMLP whose blocks are laid out as ``blocks``."""
-    col, rows, shared = 0, [], []
-    for b in blocks:
-        w = {'tri': TRI, 'pose': POSE, 'pose_rows': POSE, 'normal': NORMAL}[b]
-        (shared if b == 'pose' else rows).extend(range(col, col + w))
-        col += w
-    return rows, shared
-
-
-def params_of(fm):
-    ps = []
-    for lin, gn in fm.layers:
-        ps += [lin.weight, lin.bias, gn.weight, gn.bias]
-    for h in fm.heads:
-        ps += [h.weight, h.bias]
-    return ps
-
-
-def zero_grads(fm):
-    for p in params_of(fm):
-        p.grad = None
-
-
-def bits_equal(a, b):
-    a = np.ascontiguousarray(np.asarray(a, np.float32))
-    b = np.ascontiguousarray(np.asarray(b, np.float32))
-    return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
-
-
 def run(fm, blocks, x, G, need_x=True):
-    """Forward + backward on the GPU; returns (outs [N, nh] numpy, grads dict like the oracle's)."""
-    import exavatar_release_amd as exa  # noqa: F401
-    zero_grads(fm)
-    tri = x['tri'].clone().requires_grad_(need_x)
-    outs = fm(*block_args(x, tri, blocks))
-    outs = outs if isinstance(outs, tuple) else (outs,)
-    out = torch.cat(outs, 1)
-    gl, off = [], 0
-    for o in outs:
-        gl.append(G[:, off:off + o.shape[1]])
-        off += o.shape[1]
-    torch.autograd.backward(list(outs), gl)
-    torch.cuda.synchronize()
-    return out.detach().cpu().numpy(), tri.grad
+    """Forward + backward on the GPU; returns (outs [N, nh] numpy, the gradient of tri_feat)."""
+    out, grads = mc.run_fused(fm, [x[b] for b in blocks], G, wrt=(blocks.index('tri'),) if need_x else ())
+    return out, grads[blocks.index('tri')]
 
 
 def check_against_oracle(fm, blocks, x, G, need_x=True, need_params=True):
-    rows, shared = oracle_net(fm, blocks)
-    N = x['tri'].shape[0]
-    if not need_params:
-        for p in params_of(fm):
-            p.requires_grad_(False)
-    try:
-        out, gx = run(fm, blocks, x, G, need_x)
-    finally:
-        for p in params_of(fm):
-            p.requires_grad_(True)
-    net = mo.net_from_modules(fm.layers, fm.heads, rows, shared, x['pose'].cpu().numpy() if shared else None)
-    xin = np.concatenate([x[b].cpu().numpy() for b in blocks if b != 'pose'], 1).astype(np.float32)
-    Gn = G.cpu().numpy()
-    ref_out = mo.forward(net, xin)
-    assert bits_equal(out, ref_out), 'forward differs from the oracle (max %g)' % np.abs(out - ref_out).max()
-    if N == 0 and not need_params and not need_x:
-        return
-    ref = mo.backward(net, xin, Gn)
-    if need_x:
-        assert bits_equal(gx.cpu().numpy(), ref['x'][:, :TRI]), 'grad tri_feat differs'
-    else:
-        assert gx is None
-    if need_params:
-        for l, (lin, gn) in enumerate(fm.layers):
-            W = lin.weight.grad.cpu().numpy()
-            want = ref['layers'][l]['W']
-            if l == 0 and (shared or rows != list(range(rows[0], rows[-1] + 1))):
-                # layer 0's weight gets its gradient through several column views: autograd adds their zero-filled
-                # slice gradients, which turns an exact -0 into +0 and changes nothing else
-                want = want + np.float32(0)
-            assert bits_equal(W[:, rows] if l == 0 else W, want), 'grad W_%d differs' % l
-            if shared and l == 0:
-                assert bits_equal(W[:, shared], ref['Ws'] + np.float32(0)), 'grad of the shared columns differs'
-            assert bits_equal(lin.bias.grad.cpu(), ref['layers'][l]['b']), 'grad b_%d differs' % l
-            assert bits_equal(gn.weight.grad.cpu(), ref['layers'][l]['gamma']), 'grad gamma_%d differs' % l
-            assert bits_equal(gn.bias.grad.cpu(), ref['layers'][l]['beta']), 'grad beta_%d differs' % l
-        Wh = np.concatenate([h.weight.grad.cpu().numpy() for h in fm.heads])
-        bh = np.concatenate([h.bias.grad.cpu().numpy() for h in fm.heads])
-        assert bits_equal(Wh, ref['Wh']) and bits_equal(bh, ref['bh']), 'head gradients differ'
-    else:
-        assert all(p.grad is None for p in params_of(fm))
+    """mlp_cases.check_against_oracle over the named blocks; 'pose' is the shared (1-D) block, tri_feat the leaf."""
+    mc.check_against_oracle(fm, [x[b] for b in blocks], G, need_x, need_params, wrt=(blocks.index('tri'),))
 
 
 def make(name, nets):

@@ -6,6 +6,10 @@
   gradient and every parameter gradient, with a shared (folded) block and with a trailing Linear -- and equals the
   reference's own make_linear_layers, executed (tests/golden/ref_mlp.npz, made by tests/golden/make_golden_mlp.py:
   geo_offset_net and rgb_offset_net, the two with a shared block, one with heads and one with a trailing Linear).
+* Over the whole contract of include/exa_mlp.h (every entry of ``mlp_cases.CASES``: 1 and 4 layers, 1, 2 and 4 groups,
+  1-4 heads up to 32 wide, 1-256 per-row and 0-1024 shared columns) the float64 oracle equals PyTorch's float64
+  expression to the same 1e-12, and the fp32 oracle lies within the bound tests/test_gpu_mlp.py holds FusedMLP to.  With
+  the GPU tests, which hold the kernels to the fp32 oracle bit for bit, that gives the kernels a float64 reference there.
 * ``parse_structure`` accepts the four reference nets and refuses the unsupported ones, naming the layer."""
 import ctypes
 import ctypes.util
@@ -16,6 +20,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+import mlp_cases as mc
 import mlp_oracle as mo
 from exavatar_release_amd.mlp import parse_structure
 
@@ -138,6 +143,40 @@ def test_oracle_float64_equals_torch(case):
         _close(g['Ws'], layers[0][0].weight.grad.numpy()[:, shared], 'shared columns')
     _close(g['Wh'], np.concatenate([hd.weight.grad.numpy() for hd in hs]), 'head weights')
     _close(g['bh'], np.concatenate([hd.bias.grad.numpy() for hd in hs]), 'head biases')
+
+
+@pytest.mark.parametrize('name', sorted(mc.CASES))
+def test_oracle_float64_equals_torch_over_the_contract(name):
+    """Every entry of mlp_cases.CASES: outputs, the per-row input gradient and every parameter gradient (layer 0's weight
+    over its per-row and its shared columns, the heads stacked) against PyTorch's float64 nn.Sequential + autograd."""
+    cs = mc.case(name)
+    want = mc.torch_expression(cs.trunk, cs.heads, cs.full_input(torch.float64), cs.G, torch.float64)
+    got = mc.oracle_as_expression(cs, np.float64)
+    got, want = mc.flat(got), mc.flat(want, cs.per_row)
+    assert [k for k, _ in got] == [k for k, _ in want] and len(got) == 4 + 4 * cs.spec['L']
+    for (what, a), (_, b) in zip(got, want):
+        _close(a, b, '%s %s' % (name, what))
+
+
+@pytest.mark.parametrize('name', sorted(mc.CASES))
+def test_oracle_fp32_within_the_fp32_expression_bound(name):
+    """Every entry of mlp_cases.CASES: the fp32 oracle against the float64 expression, under the bound of
+    tests/test_gpu_mlp.py's ``_bound_check``, per result tensor, with e64 the float64 value and the fp32 expression run
+    on the CPU:
+        max |oracle_fp32 - e64| <= 16 * max |torch_fp32 - e64| + 64 * 2^-24 * rms(e64)"""
+    cs = mc.case(name)
+    e64 = mc.flat(mc.torch_expression(cs.trunk, cs.heads, cs.full_input(torch.float64), cs.G, torch.float64), cs.per_row)
+    t32 = mc.flat(mc.torch_expression(cs.trunk, cs.heads, cs.full_input(), cs.G, torch.float32), cs.per_row)
+    o32 = mc.flat(mc.oracle_as_expression(cs, np.float32))
+    for (what, a64), (_, a32), (_, ao) in zip(e64, t32, o32):
+        assert a64.shape == a32.shape == ao.shape, what
+        a64 = a64.astype(np.float64)
+        err_t = float(np.abs(a32.astype(np.float64) - a64).max())
+        err_o = float(np.abs(ao.astype(np.float64) - a64).max())
+        bound = 16 * err_t + 64 * 2.0 ** -24 * float(np.sqrt(np.mean(a64 ** 2)))
+        print('%s %s: oracle error %.3g, fp32 expression error %.3g, bound %.3g' % (name, what, err_o, err_t, bound))
+        assert err_o <= bound, '%s %s: oracle error %g > bound %g (fp32 expression error %g)' % (name, what, err_o,
+                                                                                             bound, err_t)
 
 
 def test_oracle_float64_equals_reference_golden():
