@@ -78,6 +78,11 @@ and for the face composite in front of ``rgb_face`` / ``rgb_face_refined`` and t
 ``avatar/main/model.py:200-201, 207-208, 268-276``):
 
     from exavatar_release_amd import FaceRGBLoss, face_composite, foreground_composite
+
+and for the optimizer step behind them all (``torch.optim.Adam(params, lr=0.0, eps=1e-15)`` over one group per parameter,
+reference ``avatar/common/base.py:83-85``, stepped at ``avatar/main/train.py:57``: one launch per 64 tensors):
+
+    from exavatar_release_amd import Adam, adam_step
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -100,6 +105,7 @@ from .scene_assets import scene_assets
 from .pose_params import SMPLXParamDict, pose_features, pose_params
 from .posed_body import PosedBody, PosedBodyOutput
 from .face_loss import FaceRGBLoss, face_composite, foreground_composite
+from .optim import Adam, adam_step
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -110,4 +116,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
-           'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite']
+           'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step']

@@ -102,6 +102,13 @@ class ExaRasterBackwardJob(ctypes.Structure):
     ]
 
 
+class ExaRasterAdamSegment(ctypes.Structure):
+    """One tensor of an Adam step (include/exa_raster.h): four device arrays of ``n`` floats and the two scalars of its
+    own step count and learning rate."""
+    _fields_ = [('param', c_void_p), ('grad', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p),
+                ('n', ctypes.c_int64), ('step_size', ctypes.c_float), ('bc2_sqrt', ctypes.c_float)]
+
+
 class ExaMeshGeometry(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32),
                 ('H', ctypes.c_int32), ('W', ctypes.c_int32),
@@ -256,11 +263,14 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
                              [ctypes.c_int64] + [c_void_p] * 3),
     'exa_composite_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 4 + [ctypes.c_float, c_void_p]),
     'exa_composite_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 6),
+    # the Adam step (csrc/adam.hip); `segs` is a host array
+    'exa_raster_adam_step': (ctypes.c_int, [ctypes.POINTER(ExaRasterAdamSegment), _I32, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, c_void_p]),
     'exa_raster_timing_enable': (ctypes.c_int, [_I32]),
     'exa_raster_timing_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _I32]),
     'exa_raster_timing_name': (ctypes.c_char_p, [_I32]),
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
-            ExaRasterBackwardJob))
+            ExaRasterBackwardJob, ExaRasterAdamSegment))
 
 # the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets, the forward
 # kinematics with the pose parameters in front of them, the mesh upsampling, the SMPL-X template stage, the posed SMPL-X

@@ -4,6 +4,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
+
 #include "common.h"
 
 using namespace exa;
@@ -850,6 +852,46 @@ int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const flo
     const int32_t crop[4] = {0, 0, W, H};
     EXA_HIP(launch_face_bwd(0, B, C, H, W, crop, nullptr, face, nullptr, dL_dout, nullptr, 0, dL_dimg, dL_dface,
                             static_cast<hipStream_t>(stream)), "composite_bwd");
+    return 0;
+}
+
+int exa_raster_adam_step(const ExaRasterAdamSegment* segs, int32_t n_seg, double beta1, double beta2, double eps,
+                         void* stream) {
+    if (n_seg < 0) return fail(EXA_RASTER_E_INVALID, "adam: negative n_seg");
+    if (n_seg > 0 && !segs) return fail(EXA_RASTER_E_NULLPTR, "adam: segs is NULL");
+    if (!std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps))
+        return fail(EXA_RASTER_E_INVALID, "adam: beta1, beta2 and eps must be finite");
+    if (beta1 < 0.0 || beta1 >= 1.0 || beta2 < 0.0 || beta2 >= 1.0)
+        return fail(EXA_RASTER_E_INVALID, "adam: beta1 and beta2 must be in [0, 1)");
+    if (eps < 0.0) return fail(EXA_RASTER_E_INVALID, "adam: eps must be >= 0");
+    for (int32_t s = 0; s < n_seg; ++s) {      // every segment before the first launch
+        const ExaRasterAdamSegment& g = segs[s];
+        if (g.n < 0) return fail(EXA_RASTER_E_INVALID, "adam: negative n in a segment");
+        if (g.n > EXA_RASTER_ADAM_MAX_N) return fail(EXA_RASTER_E_INVALID, "adam: more than 2^36 elements in a segment (EXA_RASTER_ADAM_MAX_N)");
+        if (g.n == 0) continue;
+        if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)
+            return fail(EXA_RASTER_E_NULLPTR, "adam: a segment with n > 0 holds a NULL pointer");
+        if (!std::isfinite(g.step_size) || !std::isfinite(g.bc2_sqrt))
+            return fail(EXA_RASTER_E_INVALID, "adam: step_size and bc2_sqrt must be finite");
+        if (!(g.bc2_sqrt > 0.0f)) return fail(EXA_RASTER_E_INVALID, "adam: bc2_sqrt must be > 0 (a step count >= 1)");
+    }
+    AdamArgs A;
+    A.w1 = (float)(1.0 - beta1); A.b2 = (float)beta2; A.w2 = (float)(1.0 - beta2); A.eps = (float)eps;
+    A.n_seg = 0;
+    A.start[0] = 0;
+    for (int32_t s = 0; s <= n_seg; ++s) {     // the non-empty segments, ADAM_MAX_SEGMENTS to a launch
+        if (s < n_seg && segs[s].n > 0) {
+            A.seg[A.n_seg] = segs[s];
+            A.start[A.n_seg + 1] = A.start[A.n_seg] + (uint32_t)((segs[s].n + EXA_RASTER_ADAM_CHUNK - 1) / EXA_RASTER_ADAM_CHUNK);
+            ++A.n_seg;
+        }
+        if (A.n_seg == ADAM_MAX_SEGMENTS || (s == n_seg && A.n_seg > 0)) {
+            for (int k = A.n_seg + 1; k <= ADAM_MAX_SEGMENTS; ++k) A.start[k] = A.start[A.n_seg];
+            for (int k = A.n_seg; k < ADAM_MAX_SEGMENTS; ++k) A.seg[k] = ExaRasterAdamSegment{};
+            EXA_HIP(launch_adam_step(A, static_cast<hipStream_t>(stream)), "adam_step");
+            A.n_seg = 0;
+        }
+    }
     return 0;
 }
 

@@ -591,5 +591,15 @@ hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, 
                            float* d_face, hipStream_t s);
 hipError_t launch_composite_fwd(int mode, int B, int C, int H, int W, const float* a, const float* sel, const float* b,
                                 float* out, float thr, hipStream_t s);
+// adam.hip: the Adam step of up to ADAM_MAX_SEGMENTS non-empty tensors, the kernel's argument block as the caller fills it
+// (everything in it is the caller's to check)
+constexpr int ADAM_MAX_SEGMENTS = 64;
+struct AdamArgs {
+    int32_t n_seg;                             // 1 .. ADAM_MAX_SEGMENTS, every one with n > 0
+    float w1, b2, w2, eps;                     // (float)(1 - beta1), (float)beta2, (float)(1 - beta2), (float)eps
+    uint32_t start[ADAM_MAX_SEGMENTS + 1];     // first chunk of every segment; start[n_seg] = the grid
+    ExaRasterAdamSegment seg[ADAM_MAX_SEGMENTS];
+};
+hipError_t launch_adam_step(const AdamArgs& A, hipStream_t s);
 
 }  // namespace exa

@@ -552,6 +552,57 @@ int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const flo
                            const float* dL_dout, float* dL_dimg, float* dL_dface, void* stream);
 
 /*
+ * The Adam step (csrc/adam.hip): `trainer.optimizer.step()` of the reference (avatar/main/train.py:57, base.py:83-85:
+ * torch.optim.Adam without weight decay or amsgrad) for any number of separately allocated tensors, one launch per
+ * EXA_RASTER_ADAM_MAX_SEGMENTS of them.  A native host applies the gradients of exa_raster_backward with it.
+ *
+ * One ExaRasterAdamSegment describes one tensor: four [dev] arrays of n contiguous floats -- param, exp_avg and
+ * exp_avg_sq are updated in place, grad is only read -- and the two scalars of the tensor's own step count t and
+ * learning rate, which the HOST forms in double and rounds once to float:
+ *     step_size = lr / (1 - beta1^t)        bc2_sqrt = sqrt(1 - beta2^t)
+ * beta1, beta2 and eps hold for the whole call; the call rounds w1 = (float)(1 - beta1), b2 = (float)beta2,
+ * w2 = (float)(1 - beta2) and e = (float)eps once.  Per element, every line one rounded fp32 operation, never fused:
+ *     m' = m + w1 * (g - m)                       when w1 < 0.5;  m' = g - (g - m) * (1 - w1) otherwise (torch's lerp)
+ *     v' = v * b2 + (w2 * g) * g
+ *     d  = sqrtf(v') / bc2_sqrt + e
+ *     p' = p + (-step_size) * (m' / d)
+ * sqrtf and / are the correctly rounded ones and subnormals are kept, so a float32 restatement on a CPU gives the same
+ * bits (tests/adam_oracle.py).  What guarantees it: the file is built without any fast-math flag and with
+ * -ffp-contract=off; hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt expands `/` to the v_div_scale / v_div_fmas
+ * / v_div_fixup sequence and sqrtf to v_sqrt_f32 plus its fused correction steps, and -fgpu-flush-denormals-to-zero is
+ * off for gfx950.  With step_size = 0 (the reference constructs its optimizer with lr = 0.0) p' = p + (-0 * x) = p bit for
+ * bit for every finite x (only a p of -0 can become +0), and the moments still advance.  g = 0 over m = v = 0 gives m' = 0, d = e and p' = p.
+ *
+ * Work split: a workgroup of 256 threads owns one chunk of EXA_RASTER_ADAM_CHUNK consecutive elements of one segment; the
+ * chunk counts of the segments lie end to end on a one-dimensional grid and a workgroup finds its segment by a binary
+ * search over the prefix counts in its kernel arguments.  The segments travel BY VALUE in the kernel arguments: no device
+ * pointer table, no workspace, no atomics, no memset, no allocation, no synchronisation, no state; the same inputs give
+ * the same bits.  A thread moves 4 consecutive floats with 16-byte loads and stores when all four arrays of its segment
+ * are 16-byte aligned; the elements of any other segment, and the last n % 4 of an aligned one, move one by one.
+ * Segments with n = 0 are skipped (their pointers are not looked at); n_seg = 0 or nothing but empty segments: no launch,
+ * returns 0.  More than EXA_RASTER_ADAM_MAX_SEGMENTS non-empty segments are issued as several launches on `stream`, in
+ * the order given.  Two segments of one call must not overlap (the caller's to ensure).
+ *
+ * Checked on the host before any launch: segs NULL with n_seg > 0, a NULL array in a segment with n > 0:
+ * EXA_RASTER_E_NULLPTR; n_seg < 0, n < 0 or n > EXA_RASTER_ADAM_MAX_N, beta1 or beta2 outside [0, 1), eps < 0, a
+ * non-finite beta1 / beta2 / eps / step_size / bc2_sqrt, bc2_sqrt <= 0 (t >= 1 makes it positive): EXA_RASTER_E_INVALID.
+ */
+#define EXA_RASTER_ADAM_MAX_SEGMENTS 64
+#define EXA_RASTER_ADAM_CHUNK 4096
+#define EXA_RASTER_ADAM_MAX_N (INT64_C(1) << 36)      /* 64 segments of it are 2^30 chunks: the grid stays below 2^31 */
+typedef struct ExaRasterAdamSegment {
+    float* param;                           /* [dev] n floats, updated in place */
+    const float* grad;                      /* [dev] n floats */
+    float* exp_avg;                         /* [dev] n floats, updated in place */
+    float* exp_avg_sq;                      /* [dev] n floats, updated in place */
+    int64_t n;
+    float step_size;                        /* (float)(lr / (1 - beta1^t)) */
+    float bc2_sqrt;                         /* (float)sqrt(1 - beta2^t) */
+} ExaRasterAdamSegment;
+int exa_raster_adam_step(const ExaRasterAdamSegment* segs, int32_t n_seg, double beta1, double beta2, double eps,
+                         void* stream);
+
+/*
  * Optional per-kernel timing for benchmarks (the only state the library ever keeps, process-wide,
  * off by default, not thread-safe).  While enabled, every kernel / memset the library enqueues is bracketed by a
  * pair of hipEvents recorded on the caller's stream.  exa_raster_timing_read() synchronises on the
