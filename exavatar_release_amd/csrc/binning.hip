@@ -4,7 +4,8 @@
 //                               count matrix; col_scan_kernel (column totals + per-chunk offsets),
 //                               cell_scan_kernel (prefix over cells), cell_scatter_kernel (entries -> buckets)
 //   digit 2 = 8x8-px sub-tile   subtile_count_kernel + subtile_bin_kernel: four workgroups per cell, counts and
-//                               ranks in LDS, emits (depth bits << 32 | id) keys grouped by sub-tile
+//                               ranks in LDS, emits (depth bits << 32 | id) keys grouped by sub-tile; the footprint
+//                               masks both walk come with the entries, from cell_scatter_kernel<true>
 //   digit 3 = depth (+ id)      sorted per sub-tile inside LDS by sort_subtiles_kernel (render_fwd.hip)
 // which reproduces the order of upstream's stable global sort on (tile << 32 | depth bits): ascending
 // depth, ties by ascending Gaussian id.  Counts travel between workgroups through plain-store matrices and
@@ -286,6 +287,48 @@ __global__ __launch_bounds__(SCAN_THREADS) void cell_scan_kernel(Batch<BinArgs> 
 // of 8 pixel rows) the sub-tiles the ellipse reaches are those whose pixel-centre range meets its x-extent inside the band
 // (common.h: make_footprint / footprint_band): O(1) per row instead of a test per sub-tile -- a large scene splat crosses up
 // to 64 sub-tiles of a cell.
+//
+// rows_mask: the sub-tiles of its cell (origin csx0, csy0 in sub-tiles) that a splat with the sub-tile rect (rx, ry) = row 3
+// words 0-1 of its record really reaches, as a 64-bit mask (bit = y * 8 + x).  r0 / r1 = rows 0-1 of the record (centre; conic
+// and opacity); r0 = r1 = 0 (A = 0): no test, the whole rect.  ONE body for every caller -- the entry-parallel scatter below,
+// which has the rows in LDS, and the counting kernels, which gather them -- so that all of them produce the same bits.
+__device__ __forceinline__ unsigned long long rows_mask(const uint4& r0, const uint4& r1, uint32_t rx, uint32_t ry, int csx0, int csy0) {
+    const int x0 = max((int)(rx & 0xffff) - csx0, 0), x1 = min((int)(rx >> 16) - csx0, CELL_SUBS);
+    const int y0 = max((int)(ry & 0xffff) - csy0, 0), y1 = min((int)(ry >> 16) - csy0, CELL_SUBS);
+    const float xl0 = (float)((csx0 + x0) * SUB) - __uint_as_float(r0.x), yl0 = (float)((csy0 + y0) * SUB) - __uint_as_float(r0.y);
+    const Footprint fp = make_footprint(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w),
+                                        fmaxf(fabsf(xl0), fabsf(xl0 + (float)((x1 - x0) * SUB))),
+                                        fmaxf(fabsf(yl0), fabsf(yl0 + (float)((y1 - y0) * SUB))));
+    unsigned long long mask = 0ull;
+    for (int y = y0; y < y1; ++y) {
+        int c0 = x0, c1 = x1 - 1;
+        if (fp.test) {
+            float xa, xb;
+            const float yl = yl0 + (float)((y - y0) * SUB);
+            if (!footprint_band(fp, yl, yl + (float)(SUB - 1), xa, xb)) continue;
+            if (xa <= xb) {                                     // (NaN: keep the row)
+                const float m = 1e-3f * (1.0f + fmaxf(fabsf(xa), fabsf(xb)));
+                const float lo = clampf((xa - m - (float)(SUB - 1) - xl0) * (1.0f / SUB), -1.0e6f, 1.0e6f);
+                const float hi = clampf((xb + m - xl0) * (1.0f / SUB), -1.0e6f, 1.0e6f);
+                c0 = max(x0, x0 + (int)ceilf(lo));
+                c1 = min(x1 - 1, x0 + (int)floorf(hi));
+            }
+        }
+        if (c1 < c0) continue;
+        mask |= (unsigned long long)((2u << c1) - (1u << c0)) << (y * CELL_SUBS);
+    }
+    return mask;
+}
+// The same for entry `en` = {id, depth, rect x, rect y} of a cell bucket: rows 0-1 gathered from the splat record.  The mask
+// replaces the rect in the entry; the scatter walks the same bits.
+template <bool FOOTPRINT>
+__device__ __forceinline__ unsigned long long entry_mask(const Splat* __restrict__ splats, const uint4& en, int csx0, int csy0) {
+    const uint4* rec = reinterpret_cast<const uint4*>(splats + en.x);
+    uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;              // (A = 0: no test, the whole rect)
+    if (FOOTPRINT) { r0 = rec[0]; r1 = rec[1]; }
+    return rows_mask(r0, r1, en.z, en.w, csx0, csy0);
+}
+
 // CHUNK Gaussians per workgroup: (a) Gaussian-major instance offsets (in-chunk prefix + chunk_off) stored
 // into the splat record, (b) 16-byte entries scattered into their cells' buckets: the chunk's first slot in
 // every cell comes from the scanned count matrix, ranks inside it from LDS atomics, (c) clears this
@@ -299,6 +342,17 @@ __device__ __forceinline__ void report_header(uint32_t* host_hdr, uint32_t need,
     const v4u v = {need, overflow, vis, tag};
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(host_hdr), "v"(v) : "memory");
 }
+// MASKS (jobs of the multi-part sub-tile binning with the footprint test on): entries leave this kernel MASK-READY, {id, depth
+// bits, mask lo, mask hi} -- the form subtile_count_kernel used to leave them in, after a divergent 32-byte gather of rows 0-1
+// of every entry's record, the fourth dependent trip of a launch of four.  Here the same rows are 1024 consecutive records,
+// loaded next to rows 2-3 under the count-matrix walk and staged in LDS (24 bytes per Gaussian).  The scatter is ENTRY-parallel:
+// every thread writes the entry of the first cell of its Gaussian's rect; a block scan of the FURTHER cells per rect numbers
+// the chunk's other entries, and the workgroup walks that numbering SC_BLOCK at a time, entry -> owning Gaussian (branch-free
+// binary search over the prefix in LDS, as stream_gather in preprocess_bwd.hip) -> cell -> LDS rank -> bucket slot.
+// No thread loops over the cells of a large splat: round 3 computed the masks Gaussian-major in
+// this kernel and lost 4 us on C3 and 55 us on C5 to the threads that walked hundreds of cells (comment above
+// subtile_count_kernel).  Slots are handed out as before: first slot of the chunk from the count matrix, rank from an LDS atomic.
+template <bool MASKS>
 __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> batch) {
     // base[cells] | cnt2[cells] (u32)  [ | tot[cells] | bef[cells] (u64) when the scans are merged into this kernel ]
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
@@ -353,6 +407,9 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
     int ids[PER];
     uint32_t depth_bits[PER];
     uint32_t mine = 0;
+    uint2 r0 = make_uint2(0u, 0u);                               // MASKS: centre (row 0) and conic + opacity (row 1) of this thread's Gaussian
+    uint4 r1 = make_uint4(0u, 0u, 0u, 0u);
+    static_assert(!MASKS || PER == 1, "the entry-parallel scatter stages one Gaussian per thread");
     auto load_rows = [&] {
 #pragma unroll
         for (int it = 0; it < PER; ++it) {
@@ -362,6 +419,10 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
             if (ids[it] < P) {
                 r3[it] = reinterpret_cast<const uint4*>(splats + ids[it])[3];
                 depth_bits[it] = reinterpret_cast<const uint4*>(splats + ids[it])[2].w;
+                if (MASKS) {                                     // (the other half of the same 64-byte line)
+                    r0 = reinterpret_cast<const uint2*>(splats + ids[it])[0];
+                    r1 = reinterpret_cast<const uint4*>(splats + ids[it])[1];
+                }
             }
         }
     };
@@ -472,6 +533,56 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
     }
     __syncthreads();
 
+    if constexpr (MASKS) {
+        __shared__ uint32_t s_pre[SC_BLOCK];                     // walked entries of the chunk in front of those of Gaussian g
+        __shared__ uint2 s_rect[SC_BLOCK], s_ctr[SC_BLOCK];      // rect words of row 3; pixel centre
+        __shared__ uint4 s_con[SC_BLOCK];                        // conic and opacity
+        __shared__ uint32_t s_dep[SC_BLOCK];
+        const uint32_t rx = r3[0].x, ry = r3[0].y;
+        // cells the rect spans (a Gaussian without instances has no entries)
+        const uint32_t ncell = r3[0].z ? (uint32_t)((((int)(rx >> 16) - 1) >> 3) - (int)((rx & 0xffff) >> 3) + 1) *
+                                             (uint32_t)((((int)(ry >> 16) - 1) >> 3) - (int)((ry & 0xffff) >> 3) + 1) : 0u;
+        // Every Gaussian writes the entry of the FIRST cell of its rect itself, from its registers; the walk numbers the others.
+        // (Walking all entries cost C3 +2.6 us here: an avatar chunk has ~1 100 entries, nine in ten the only one of their
+        //  splat, and they paid the search and a second, nearly empty tile.  profiles/binning_masks_ab.md, variant 1a.)
+        const uint32_t more = ncell ? ncell - 1u : 0u;
+        // further entries << 32 | instances: the in-chunk prefixes of both behind one pair of barriers
+        unsigned long long tot;
+        const unsigned long long x = block_excl_scan64(((unsigned long long)more << 32) | r3[0].z, s_tmp64, tot);
+        if (r3[0].z) splats[ids[0]].inst_off = chunk_off + (uint32_t)x;
+        s_pre[tid] = (uint32_t)(x >> 32);
+        s_rect[tid] = make_uint2(rx, ry);
+        s_ctr[tid] = r0;
+        s_con[tid] = r1;
+        s_dep[tid] = depth_bits[0];
+        __syncthreads();
+        SCATTER_PHASE(3);                                        // splat rows staged, in-chunk prefixes
+        // entry of cell k (row-major inside the rect's cells) of a Gaussian: LDS rank -> bucket slot, mask from its rows
+        auto emit = [&](uint32_t id, uint32_t dep, const uint2& ctr, const uint4& con, uint32_t ex, uint32_t ey, uint32_t k) {
+            const int cx0 = (int)((ex & 0xffff) >> 3), cw = ((((int)(ex >> 16)) - 1) >> 3) - cx0 + 1;
+            const int dy = (int)(k / (uint32_t)cw);
+            const int cx = cx0 + ((int)k - dy * cw), cy = (int)((ey & 0xffff) >> 3) + dy;
+            const int c = cy * gcx + cx;
+            const uint32_t r = __hip_atomic_fetch_add(&s_cnt2[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const unsigned long long mask = rows_mask(make_uint4(ctr.x, ctr.y, 0u, 0u), con, ex, ey, cx * CELL_SUBS, cy * CELL_SUBS);
+            bucket[s_base[c] + r] = make_uint4(id, dep, (uint32_t)mask, (uint32_t)(mask >> 32));
+        };
+        if (ncell) emit((uint32_t)ids[0], depth_bits[0], r0, r1, rx, ry, 0u);
+        const uint32_t E = (uint32_t)(tot >> 32);
+        for (uint32_t q = tid; q < E; q += SC_BLOCK) {
+            // the LAST Gaussian g with pre[g] <= q owns entry q (those without further entries share their successor's prefix).
+            // (Four-way steps -- five dependent LDS levels instead of ten -- with the first tile's search requested in front of
+            //  the threads' own entries changed nothing: 15.28 against 15.16 us.  The search is not what this kernel waits for.)
+            uint32_t g = 0;
+#pragma unroll
+            for (int s2 = SC_BLOCK / 2; s2 > 0; s2 >>= 1)
+                if (s_pre[g + s2] <= q) g += s2;
+            const uint2 rect = s_rect[g];
+            emit((uint32_t)(blockIdx.x * CHUNK) + g, s_dep[g], s_ctr[g], s_con[g], rect.x, rect.y, q - s_pre[g] + 1u);
+        }
+        SCATTER_PHASE(4);                                        // entries scattered
+        return;
+    }
 #pragma unroll
     for (int it = 0; it < PER; ++it) mine += r3[it].z;
     uint32_t total;
@@ -510,7 +621,11 @@ constexpr int BIN_THREADS = 1024;
 // (Round 3 tried ONE launch: footprint masks computed by cell_scatter_kernel -- the record is in registers there -- and
 //  every part counting the whole cell itself.  Bitwise the same lists, but slower: the mask work is Gaussian-major there,
 //  one thread walks ALL cells of its splat -- C3 cell_scatter 18.4 -> 22.8 us for 19.7 -> 16.8 us here, C5 (scene splats
-//  over hundreds of cells) 20.7 -> 76 us.  Entry-parallel masks in their own launch stay.)
+//  over hundreds of cells) 20.7 -> 76 us.  Since then the masks ARE computed in cell_scatter_kernel, entry-parallel
+//  (cell_scatter_kernel<true>, mask-ready entries), and the one launch was measured again on them: every part reads the mask
+//  words of its whole cell, four loads in flight, one LDS atomic per mask bit.  13.6 us against 4.9 + 6.8 for the two launches
+//  below: with the adaptive part table a part of an n-part cell counts n times the entries, up to sixteen times.  Not in the
+//  tree; profiles/binning_masks_ab.md.)
 // (Round 3 also tried to fuse the scatter below with the SORT of the lists (commit 10d6018, removed again): one 512-thread
 //  workgroup per row of eight sub-tiles scans the cell's entries, keeps the keys of its row in LDS and every wave sorts one
 //  list.  The keys never touch HBM and one launch goes, but it is slower -- count 11.6 + fused 30 us against bin 19.6 +
@@ -552,41 +667,9 @@ __device__ __forceinline__ CellPart cell_part(const uint4& d, uint32_t active, u
     return c;
 }
 
-// The sub-tiles of its cell (origin csx0, csy0 in sub-tiles) that the footprint of entry `en` = {id, depth, rect x, rect y}
-// really reaches, as a 64-bit mask (bit = y * 8 + x).  It replaces the rect in the entry; the scatter walks the same bits.
-template <bool FOOTPRINT>
-__device__ __forceinline__ unsigned long long entry_mask(const Splat* __restrict__ splats, const uint4& en, int csx0, int csy0) {
-    const uint4* rec = reinterpret_cast<const uint4*>(splats + en.x);
-    uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;              // (A = 0: no test, the whole rect)
-    if (FOOTPRINT) { r0 = rec[0]; r1 = rec[1]; }
-    const int x0 = max((int)(en.z & 0xffff) - csx0, 0), x1 = min((int)(en.z >> 16) - csx0, CELL_SUBS);
-    const int y0 = max((int)(en.w & 0xffff) - csy0, 0), y1 = min((int)(en.w >> 16) - csy0, CELL_SUBS);
-    const float xl0 = (float)((csx0 + x0) * SUB) - __uint_as_float(r0.x), yl0 = (float)((csy0 + y0) * SUB) - __uint_as_float(r0.y);
-    const Footprint fp = make_footprint(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w),
-                                        fmaxf(fabsf(xl0), fabsf(xl0 + (float)((x1 - x0) * SUB))),
-                                        fmaxf(fabsf(yl0), fabsf(yl0 + (float)((y1 - y0) * SUB))));
-    unsigned long long mask = 0ull;
-    for (int y = y0; y < y1; ++y) {
-        int c0 = x0, c1 = x1 - 1;
-        if (fp.test) {
-            float xa, xb;
-            const float yl = yl0 + (float)((y - y0) * SUB);
-            if (!footprint_band(fp, yl, yl + (float)(SUB - 1), xa, xb)) continue;
-            if (xa <= xb) {                                     // (NaN: keep the row)
-                const float m = 1e-3f * (1.0f + fmaxf(fabsf(xa), fabsf(xb)));
-                const float lo = clampf((xa - m - (float)(SUB - 1) - xl0) * (1.0f / SUB), -1.0e6f, 1.0e6f);
-                const float hi = clampf((xb + m - xl0) * (1.0f / SUB), -1.0e6f, 1.0e6f);
-                c0 = max(x0, x0 + (int)ceilf(lo));
-                c1 = min(x1 - 1, x0 + (int)floorf(hi));
-            }
-        }
-        if (c1 < c0) continue;
-        mask |= (unsigned long long)((2u << c1) - (1u << c0)) << (y * CELL_SUBS);
-    }
-    return mask;
-}
-
-template <bool FOOTPRINT, int PARTS>
+// READY: the entries come mask-ready from cell_scatter_kernel<true>: one load per entry (its two mask words) and the LDS
+// atomics over the mask bits -- no record gather, no mask arithmetic, no store back.
+template <bool FOOTPRINT, int PARTS, bool READY = false>
 __global__ __launch_bounds__(BIN_THREADS) void subtile_count_kernel(Batch<BinArgs> batch) {
     __shared__ uint32_t s_cnt[SUBS_PER_CELL];
     const BinArgs& a = batch.v[blockIdx.y];
@@ -613,6 +696,12 @@ __global__ __launch_bounds__(BIN_THREADS) void subtile_count_kernel(Batch<BinArg
     __syncthreads();
     const int csx0 = (cp.cell % gcx) * CELL_SUBS, csy0 = (cp.cell / gcx) * CELL_SUBS;   // cell origin in sub-tiles
     for (uint32_t e = cp.lo + tid; e < cp.hi; e += BIN_THREADS) {
+        if (READY) {
+            const uint2 mw = reinterpret_cast<const uint2*>(bucket + e)[1];
+            for (unsigned long long m = ((unsigned long long)mw.y << 32) | mw.x; m; m &= m - 1)
+                __hip_atomic_fetch_add(&s_cnt[__builtin_ctzll(m)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            continue;
+        }
         // ONE 16-byte load of the entry: left to itself the compiler fetched the rect words first and sank the id word
         // into the block that uses it -- behind a wait: a fourth dependent round trip in a launch that consists of four
         uint4 en = bucket[e];
@@ -803,6 +892,21 @@ hipError_t launch_cell_scan(const BinArgs* a, int K, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Which launches of a batch (cells = the largest cell count of its jobs) take the multi-part sub-tile binning, and which of
+// those hand over MASK-READY entries (cell_scatter_kernel<true> -> subtile_count_kernel<.., true>): the footprint test on,
+// and the staged rows of a chunk (40 bytes per Gaussian + the scans' scratch) next to the per-cell arrays within the 64 KB
+// of LDS a workgroup may have.  Both launchers ask here, so that producer and consumer of the entries always agree.
+#ifndef EXA_MASK_READY
+#define EXA_MASK_READY 1                // 0 (build-time, tools/build_variant.sh): masks by subtile_count_kernel, as before
+#endif
+constexpr size_t SCATTER_STAGE_LDS = (size_t)SC_BLOCK * 40 + 512;
+static bool multi_part_binning(int cells) {
+    return !(cells >= dev_knobs().single_cells || cells > 1024);  // (the part table maps one thread to one cell)
+}
+static bool mask_ready_entries(int cells) {
+    return EXA_MASK_READY && dev_knobs().footprint && multi_part_binning(cells) && (size_t)cells * 24 + SCATTER_STAGE_LDS <= 65536;
+}
+
 hipError_t launch_cell_scatter(const BinArgs* a, int K, hipStream_t s) {
     const Batch<BinArgs> b = make_batch(a, K);
     int chunks = 0, cells = 0;
@@ -813,7 +917,9 @@ hipError_t launch_cell_scatter(const BinArgs* a, int K, hipStream_t s) {
     // one workgroup past the last chunk: the publisher of the merged scans; without them at least one workgroup per job,
     // which clears the zero-filled section
     chunks = a[0].merged ? chunks + 1 : max(chunks, 1);
-    cell_scatter_kernel<<<dim3(chunks, K), SC_BLOCK, (size_t)cells * (a[0].merged ? 24 : 8), s>>>(b);
+    const size_t dyn = (size_t)cells * (a[0].merged ? 24 : 8);
+    if (mask_ready_entries(cells)) cell_scatter_kernel<true><<<dim3(chunks, K), SC_BLOCK, dyn, s>>>(b);
+    else cell_scatter_kernel<false><<<dim3(chunks, K), SC_BLOCK, dyn, s>>>(b);
     return hipGetLastError();
 }
 
@@ -826,12 +932,12 @@ hipError_t launch_subtile_bin(const BinArgs* a, int K, hipStream_t s) {
     // Workgroups per cell: an avatar view fills a few dozen of its 256 cells, so every cell is split over BIN_PARTS
     // workgroups (two launches) to get the chip busy; a large image (C5: 1024 cells, content everywhere) has enough
     // cells already and takes one workgroup per cell that counts and scatters in ONE launch.
-    const int single_cells = dev_knobs().single_cells;
-    if (cells >= single_cells || cells > 1024) {                  // (the part table maps one thread to one cell)
+    if (!multi_part_binning(cells)) {
         if (footprint) subtile_count_bin_kernel<true><<<dim3(cells, K), BIN_THREADS, 0, s>>>(b);
         else subtile_count_bin_kernel<false><<<dim3(cells, K), BIN_THREADS, 0, s>>>(b);
     } else {
-        if (footprint) subtile_count_kernel<true, BIN_PARTS><<<dim3(cells * BIN_PARTS, K), BIN_THREADS, 0, s>>>(b);
+        if (mask_ready_entries(cells)) subtile_count_kernel<true, BIN_PARTS, true><<<dim3(cells * BIN_PARTS, K), BIN_THREADS, 0, s>>>(b);
+        else if (footprint) subtile_count_kernel<true, BIN_PARTS><<<dim3(cells * BIN_PARTS, K), BIN_THREADS, 0, s>>>(b);
         else subtile_count_kernel<false, BIN_PARTS><<<dim3(cells * BIN_PARTS, K), BIN_THREADS, 0, s>>>(b);
         subtile_bin_kernel<BIN_PARTS><<<dim3(cells * BIN_PARTS, K), BIN_THREADS, 0, s>>>(b);
     }
