@@ -23,13 +23,25 @@ namespace exa {
 constexpr int SCAN_THREADS = 1024;
 constexpr int SC_BLOCK_THREADS = 1024;   // = SC_BLOCK (cell_scatter_kernel), declared further down
 
+// Wave-wide inclusive scans on the DPP path of the VALU: the value of the lane `d` below inside a row of 16 lanes (row_shr,
+// d = 1 2 4 8), then lane 15 of rows 0 and 2 added to all of rows 1 and 3 (row_bcast:15), then lane 31 to the upper half
+// (row_bcast:31) -- six dependent VALU operations.  A lane without a source (the first d of a row, the rows a row mask
+// leaves out) receives the zero passed as the old value.  Through __shfl_up the same six steps are six dependent
+// ds_bpermute round trips through the LDS crossbar (twelve for 64 bits); in cell_scatter_kernel, three scans deep, that
+// chain and not the barriers was what the scan phases took (phase probe, profiles/scatter_overlap_ab.md).  Integer sums
+// in another order: the same result.  All 64 lanes of the wave must be active, as before.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+constexpr int DPP_ROW_SHR = 0x110, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t n = __shfl_up(v, d, 64);
-        if (lane >= d) v += n;
-    }
+    v += dpp_or_zero<DPP_ROW_SHR + 1, 0xf>(v);
+    v += dpp_or_zero<DPP_ROW_SHR + 2, 0xf>(v);
+    v += dpp_or_zero<DPP_ROW_SHR + 4, 0xf>(v);
+    v += dpp_or_zero<DPP_ROW_SHR + 8, 0xf>(v);
+    v += dpp_or_zero<DPP_ROW_BCAST15, 0xa>(v);
+    v += dpp_or_zero<DPP_ROW_BCAST31, 0xc>(v);
     return v;
 }
 
@@ -97,13 +109,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void col_scan_kernel(Batch<BinArgs> b
 
 // One workgroup: exclusive prefix of the per-cell (entries, instances) totals and of the per-chunk instance
 // counts, the header, the LPT order of the cells.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_or_zero64(unsigned long long v) {
+    return ((unsigned long long)dpp_or_zero<CTRL, ROW_MASK>((uint32_t)(v >> 32)) << 32) | dpp_or_zero<CTRL, ROW_MASK>((uint32_t)v);
+}
 __device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long n = __shfl_up(v, d, 64);
-        if (lane >= d) v += n;
-    }
+    v += dpp_or_zero64<DPP_ROW_SHR + 1, 0xf>(v);
+    v += dpp_or_zero64<DPP_ROW_SHR + 2, 0xf>(v);
+    v += dpp_or_zero64<DPP_ROW_SHR + 4, 0xf>(v);
+    v += dpp_or_zero64<DPP_ROW_SHR + 8, 0xf>(v);
+    v += dpp_or_zero64<DPP_ROW_BCAST15, 0xa>(v);
+    v += dpp_or_zero64<DPP_ROW_BCAST31, 0xc>(v);
     return v;
 }
 // exclusive scan of two 32-bit counters packed in one u64 (no carry between the halves: both sums stay < 2^32)
@@ -352,6 +368,16 @@ __device__ __forceinline__ void report_header(uint32_t* host_hdr, uint32_t need,
 // No thread loops over the cells of a large splat: round 3 computed the masks Gaussian-major in
 // this kernel and lost 4 us on C3 and 55 us on C5 to the threads that walked hundreds of cells (comment above
 // subtile_count_kernel).  Slots are handed out as before: first slot of the chunk from the count matrix, rank from an LDS atomic.
+// Phases of a scattering workgroup on C3 (tools/gpu_scatter_phases.py, profiles/scatter_overlap_ab.md), us: prologue and
+// zero-fill 0.6 | column walk 4.8 | the two block scans 1.3 | rows, 64-bit in-chunk scan, staging 1.6 | masks and entries 3.1;
+// the publisher ends ~1.5 us before them.  The ORDER is the one that measured best.  Built and not kept, each slower than
+// this (15.4 / 15.8 / 15.3 against 15.1 us before the wave scans went to DPP, 14.3 against 14.2 after): the zero-fill behind
+// the last load request (its stores were never what the walk's first wait waited for, and behind them the first use of the
+// rows waits for vmcnt(0)); the rows requested FIRST and the first-cell masks computed with four trips of the walk in flight
+// (the walk is where the memory system is the limit: with 147 workgroups fetching their records in front of it, it takes
+// 6.4 us instead of 4.8 -- the publisher's too -- for 0.6 us of arithmetic less at the end); the in-chunk scan folded into
+// block_excl_scan_pair (two barriers fewer, and the scan phase 0.9 us LONGER while a 64-bit wave scan was twelve dependent
+// ds_bpermute: the wave scans, not the barriers, were what the scan phases took -- wave_incl_scan above).
 template <bool MASKS>
 __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> batch) {
     // base[cells] | cnt2[cells] (u32)  [ | tot[cells] | bef[cells] (u64) when the scans are merged into this kernel ]
