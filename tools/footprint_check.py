@@ -1,12 +1,20 @@
-"""Developer check (CPU, numpy float32): the row-interval footprint arithmetic of csrc/binning.hip (subtile_count_kernel)
-against the per-pixel alpha rule evaluated by brute force on one 64x64 cell -- no reached sub-tile may be missed ("bad" must be
-0); "kept" vs "exact(pixel)" shows how tight the test is, "box" what the bounding rect alone keeps.  python tools/footprint_check.py"""
+"""Developer check (CPU, numpy float32): the row-interval footprint arithmetic of csrc/binning.hip (rows_mask; the model is
+tests/footprint_oracle.py model_cell_masks) against the per-pixel alpha rule evaluated by brute force on one 64x64 cell -- no
+reached sub-tile may be missed ("bad" must be 0); "kept" vs "exact(pixel)" shows how tight the test is, "box" what the bounding
+rect alone keeps.  python tools/footprint_check.py"""
+import os
+import sys
+
 import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+import footprint_oracle as fo                                                # noqa: E402
+
 rng = np.random.default_rng(0)
 f32 = np.float32
 LOG2E = f32(1.4426950408889634)
 def run(N, big):
-    bad = 0; kept = 0; exact = 0; box = 0
+    recs = []; truths = []; what = []
     for it in range(N):
         # random covariance (with the 0.3 low-pass), opacity, centre
         s1 = np.exp(rng.uniform(np.log(0.3), np.log(60.0 if big else 6.0))); s2 = np.exp(rng.uniform(np.log(0.3), np.log(60.0 if big else 6.0)))
@@ -34,37 +42,18 @@ def run(N, big):
         x0 = max(int(np.floor((px - ex) / 8)), 0); x1 = min(int(np.floor(np.ceil(px + ex) / 8)) + 1, 8)
         y0 = max(int(np.floor((py - ey) / 8)), 0); y1 = min(int(np.floor(np.ceil(py + ey) / 8)) + 1, 8)
         if x1 <= x0 or y1 <= y0: continue
-        # ---- row-interval method in float32 ----
-        xl0 = f32(x0 * 8) - px; yl0 = f32(y0 * 8) - py
-        xm = max(abs(xl0), abs(xl0 + f32((x1 - x0) * 8))); ym = max(abs(yl0), abs(yl0 + f32((y1 - y0) * 8)))
-        mag = abs(A) * xm * xm + abs(B) * xm * ym + abs(C) * ym * ym
-        thr = f32(-np.log2(f32(255.0) * f32(op))) - f32(1e-3) - f32(1e-5) * f32(mag)
-        rA = f32(1) / A; rC = f32(1) / C
-        As = A - f32(0.25) * B * B * rC
-        mask = np.zeros((8, 8), bool)
-        if not (A < 0 and C < 0 and As < 0):
-            mask[y0:y1, x0:x1] = True
-        else:
-            kA = f32(-0.5) * B * rA; kC = f32(-0.5) * B * rC
-            Xf = np.sqrt(thr / As, dtype=np.float32)
-            ysr = kC * Xf
-            X2 = thr * rA
-            D4 = C * As * rA * rA
-            for y in range(y0, y1):
-                yl = yl0 + f32((y - y0) * 8); yh = yl + f32(7)
-                yR = min(max(ysr, yl), yh); yL = min(max(-ysr, yl), yh)
-                hR2 = X2 - D4 * yR * yR; hL2 = X2 - D4 * yL * yL
-                if hR2 < 0 or hL2 < 0: continue
-                xb = kA * yR + np.sqrt(hR2, dtype=np.float32); xa = kA * yL - np.sqrt(hL2, dtype=np.float32)
-                m = f32(1e-3) * (f32(1) + max(abs(xa), abs(xb)))
-                clo = x0 + int(np.ceil((xa - m - f32(7) - xl0) * f32(0.125)))
-                chi = x0 + int(np.floor((xb + m - xl0) * f32(0.125)))
-                clo = max(clo, x0); chi = min(chi, x1 - 1)
-                if chi >= clo: mask[y, clo:chi + 1] = True
-        miss = truth & ~mask
+        recs.append((px, py, 1, A, B, C, f32(op), x0, x1, y0, y1)); truths.append(truth); what.append((it, s1, s2, th, op, px, py))
+    # ---- row-interval method in float32: the model of make_footprint / footprint_band / rows_mask, one cell at the origin ----
+    rec = fo.pack(*(np.array(col) for col in zip(*recs)))
+    g = np.arange(len(rec)); zero = np.zeros(len(rec), np.int64)
+    masks = fo.model_cell_masks(rec, g, zero, zero)
+    r = fo.unpack(rec)
+    bad = 0
+    for k in range(len(rec)):
+        miss = truths[k] & ~masks[k]
         # truth outside the rect cannot happen if the rect is right
-        if miss.any(): bad += 1; print('MISS', it, s1, s2, th, op, px, py, np.argwhere(miss)[:3])
-        kept += mask.sum(); exact += truth.sum(); box += (y1 - y0) * (x1 - x0)
+        if miss.any(): bad += 1; print('MISS', *what[k], np.argwhere(miss)[:3])
+    kept = masks.sum(); exact = np.sum(truths); box = r['n_inst'].sum()
     print('N', N, 'big', big, 'bad', bad, 'box', box, 'kept', kept, 'exact(pixel)', exact)
 run(4000, False)
 run(3000, True)
