@@ -83,10 +83,17 @@ and for the optimizer step behind them all (``torch.optim.Adam(params, lr=0.0, e
 reference ``avatar/common/base.py:83-85``, stepped at ``avatar/main/train.py:57``: one launch per 64 tensors):
 
     from exavatar_release_amd import Adam, adam_step
+
+and for the scene module that holds them together, with the one operation that changes P (``SceneGaussian`` with
+``densify_and_prune`` / ``prune_points``: clone, split and prune decided per source row and carried out as one move of the
+six parameters and their Adam moments, one host synchronisation; reference ``avatar/common/nets/module.py:17-72,74-272``,
+called at ``avatar/main/model.py:279-292``):
+
+    from exavatar_release_amd import SceneGaussian, densify_plan, densify_apply, prune_plan
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
-from .densify import track_densify_stats
+from .densify import DensifyPlan, densify_apply, densify_plan, prune_plan, track_densify_stats
 from .losses import SSIM, PhotometricLoss, RGBLoss
 from .renderer import ITERATION_RENDERS, GaussianRenderer, GraphedRenderer, render_iteration, render_many, render_views
 from .graphed import GraphedIteration
@@ -106,6 +113,7 @@ from .pose_params import SMPLXParamDict, pose_features, pose_params
 from .posed_body import PosedBody, PosedBodyOutput
 from .face_loss import FaceRGBLoss, face_composite, foreground_composite
 from .optim import Adam, adam_step
+from .scene_gaussian import SceneGaussian
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -116,4 +124,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'blend_offsets', 'joint_transforms', 'batch_rigid_transform', 'BodyTemplate', 'BodyOutput', 'MeshUpsampler',
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
-           'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step']
+           'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step',
+           'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan']

@@ -109,6 +109,13 @@ class ExaRasterAdamSegment(ctypes.Structure):
                 ('n', ctypes.c_int64), ('step_size', ctypes.c_float), ('bc2_sqrt', ctypes.c_float)]
 
 
+class ExaRasterDensifySegment(ctypes.Structure):
+    """One tensor of a densification move (include/exa_raster.h): ``src`` holds P0 rows of ``row_floats`` floats, ``dst``
+    has room for ``dst_rows`` rows; ``role`` is one of ``DENSIFY_COPY`` / ``_STATE`` / ``_MEAN`` / ``_SCALE``."""
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('row_floats', ctypes.c_int64), ('dst_rows', ctypes.c_int64),
+                ('role', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class ExaMeshGeometry(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32),
                 ('H', ctypes.c_int32), ('W', ctypes.c_int32),
@@ -174,6 +181,10 @@ STORE_CTX, STAGE_NO_BLEND, STAGE_BLEND_ONLY, STAGE_NO_SORT, STAGE_SORT_ONLY = 1,
 TIMING_SLOTS = 9
 KNN_NO_CULL = 1      # EXA_KNN_NO_CULL
 COMPOSITE_FACE_HARD, COMPOSITE_FACE_SOFT, COMPOSITE_FOREGROUND = 0, 1, 2      # EXA_COMPOSITE_*
+
+DENSIFY_MAX_SEGMENTS, DENSIFY_BLOCK, DENSIFY_SCAN = 64, 256, 256        # EXA_RASTER_DENSIFY_MAX_SEGMENTS / _BLOCK / _SCAN
+DENSIFY_KEEP, DENSIFY_CLONE, DENSIFY_SPLIT, DENSIFY_CAND = 1, 2, 4, 8      # the bits of a row's code
+DENSIFY_COPY, DENSIFY_STATE, DENSIFY_MEAN, DENSIFY_SCALE = 0, 1, 2, 3      # the roles of a segment
 
 
 class Abi:
@@ -266,11 +277,17 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
     # the Adam step (csrc/adam.hip); `segs` is a host array
     'exa_raster_adam_step': (ctypes.c_int, [ctypes.POINTER(ExaRasterAdamSegment), _I32, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, c_void_p]),
+    # the densification (csrc/densify.hip); `segs` is a host array
+    'exa_raster_densify_workspace_size': (ctypes.c_int, [_I32, _U64P]),
+    'exa_raster_densify_plan': (ctypes.c_int, [_I32] + [c_void_p] * 7 + [ctypes.c_double] * 3 + [_I32, _I32, ctypes.c_double,
+                                                                                                c_void_p, _U64, c_void_p]),
+    'exa_raster_densify_move': (ctypes.c_int, [_I32, _I32, c_void_p, _U64, _I32, _I32, _I32, _I32,
+                                               ctypes.POINTER(ExaRasterDensifySegment), _I32] + [c_void_p] * 4),
     'exa_raster_timing_enable': (ctypes.c_int, [_I32]),
     'exa_raster_timing_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), _I32]),
     'exa_raster_timing_name': (ctypes.c_char_p, [_I32]),
 }, _by_name(ExaRasterSettings, ExaRasterWorkspaceSizes, ExaRasterHeader, ExaRasterForwardJob, ExaRasterComposeJob,
-            ExaRasterBackwardJob, ExaRasterAdamSegment))
+            ExaRasterBackwardJob, ExaRasterAdamSegment, ExaRasterDensifySegment))
 
 # the triangle rasterizer of the face render, the mesh Laplacian regulariser, the blend-shape offsets, the forward
 # kinematics with the pose parameters in front of them, the mesh upsampling, the SMPL-X template stage, the posed SMPL-X
@@ -412,6 +429,10 @@ def sizes_query(abi, name, struct, *args):
 
 def skin_workspace_size(V, J):
     return size_query(SKIN, 'exa_skin_workspace_size', V, J)
+
+
+def densify_workspace_size(P0):
+    return size_query(RASTER, 'exa_raster_densify_workspace_size', P0)
 
 
 def knn_workspace_size(N, P1, P2, K):

@@ -65,6 +65,8 @@ SOURCES = {
     'face_loss.hip': ['-ffp-contract=off'],
     # the Adam step is defined operation by operation (include/exa_raster.h)
     'adam.hip': ['-ffp-contract=off'],
+    # the densification's decisions and children are defined operation by operation (include/exa_raster.h)
+    'densify.hip': ['-ffp-contract=off'],
 }
 
 

@@ -601,5 +601,30 @@ struct AdamArgs {
     ExaRasterAdamSegment seg[ADAM_MAX_SEGMENTS];
 };
 hipError_t launch_adam_step(const AdamArgs& A, hipStream_t s);
+// densify.hip: the classification with its scan, and the move of up to DENSIFY_MAX_SEGMENTS tensors; the argument blocks as
+// the caller fills them (everything in them is the caller's to check)
+constexpr int DENSIFY_MAX_SEGMENTS = 64;
+struct DensifyPlanArgs {
+    int32_t P0;
+    int32_t prune_big;
+    const float *grad_accum, *track_cnt, *scale, *opacity;
+    const float* radius_max;                   // NULL: no screen-space rule
+    const float* extent;
+    const uint8_t* mask;                       // not NULL: mask mode, the six pointers above are not looked at
+    float grad_thr, dense_percent, opacity_min, child_div, screen_size_max;
+    uint8_t* codes;                            // the sections of the workspace
+    uint4* counts;
+};
+struct DensifyMoveArgs {
+    int32_t P0, split_factor, n_keep, n_clone, n_split, n_cand, n_seg;
+    float child_div;                           // (float)(0.8 * split_factor)
+    const uint4* record;                       // the sections of the workspace
+    const uint4* offsets;
+    const uint8_t* codes;
+    const float *rotation, *scale, *noise;     // the children's sources
+    ExaRasterDensifySegment seg[DENSIFY_MAX_SEGMENTS];
+};
+hipError_t launch_densify_plan(const DensifyPlanArgs& A, uint4* record, hipStream_t s);
+hipError_t launch_densify_move(const DensifyMoveArgs& A, hipStream_t s);
 
 }  // namespace exa

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define EXA_RASTER_VERSION 139          /* 0.1.3.9: tile_bytes of exa_raster_workspace_sizes grew (launch-order cursors per XCD region, one class code per sub-tile); no signature changed; 0.1.3.8: grad_bytes of exa_raster_workspace_sizes includes the 92 B x P group scratch of summed batches of more than four views; 0.1.3.7: ExaRasterComposeJob.radii_out / is_vis_out; 0.1.3.6: exa_raster_select_row; 0.1.3.5: EXA_RASTER_STAGE_* bits of store_ctx; 0.1.3.4: ExaRasterBackwardJob.used_slots; 0.1.3.3: ExaRasterForwardJob.is_vis, ExaRasterBackwardJob.accumulate; 0.1.3.2: ExaRasterBackwardJob.dL_dcolor_indirect, exa_raster_store_pointers, ExaRasterComposeJob.a_color .. a_bg; 0.1.3.1: composite renders (exa_raster_forward_compose_batch); 0.1.3: header.num_tile_instances, EXA_RASTER_E_OVERFLOW / _E_ALIAS, exa_raster_camera_block,
+#define EXA_RASTER_VERSION 139          /* 0.1.3.9: exa_raster_densify_workspace_size / _plan / _move and ExaRasterDensifySegment were added under this number, as exa_raster_adam_step was (new functions only: nothing that existed changed, and tests/test_abi.py pins 139); tile_bytes of exa_raster_workspace_sizes grew (launch-order cursors per XCD region, one class code per sub-tile); no signature changed; 0.1.3.8: grad_bytes of exa_raster_workspace_sizes includes the 92 B x P group scratch of summed batches of more than four views; 0.1.3.7: ExaRasterComposeJob.radii_out / is_vis_out; 0.1.3.6: exa_raster_select_row; 0.1.3.5: EXA_RASTER_STAGE_* bits of store_ctx; 0.1.3.4: ExaRasterBackwardJob.used_slots; 0.1.3.3: ExaRasterForwardJob.is_vis, ExaRasterBackwardJob.accumulate; 0.1.3.2: ExaRasterBackwardJob.dL_dcolor_indirect, exa_raster_store_pointers, ExaRasterComposeJob.a_color .. a_bg; 0.1.3.1: composite renders (exa_raster_forward_compose_batch); 0.1.3: header.num_tile_instances, EXA_RASTER_E_OVERFLOW / _E_ALIAS, exa_raster_camera_block,
                                            exa_raster_header_status; 0.1.2: ExaRasterBackwardJob.grad_first; .1: exa_raster_read_header_async */
 #define EXA_RASTER_TILE 16              /* 16x16 pixel tiles (upstream BLOCK_X/BLOCK_Y) */
 
@@ -601,6 +601,98 @@ typedef struct ExaRasterAdamSegment {
 } ExaRasterAdamSegment;
 int exa_raster_adam_step(const ExaRasterAdamSegment* segs, int32_t n_seg, double beta1, double beta2, double eps,
                          void* stream);
+
+/*
+ * Densification (csrc/densify.hip): the clone, split and prune passes of the reference's SceneGaussian.densify_and_prune
+ * (avatar/common/nets/module.py:159-245) decided once per SOURCE row and carried out as one move of all rows.  That is
+ * possible because clones never split (their padded gradient is zero, module.py:191-192), clones and split children inherit
+ * their source's opacity, and a child's scale is a function of its source's scale.
+ *
+ * exa_raster_densify_plan classifies the P0 rows and scans the counts; it enqueues two launches and does not synchronise.
+ * Per row i, every line one rounded fp32 operation (the doubles of the call are rounded to float once, as CPU torch rounds
+ * Python scalars against float32 tensors):
+ *     g    = grad_accum[i] / track_cnt[i];  NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX          (nan_to_num)
+ *     hot  = g >= (float)grad_thr
+ *     m    = max_k expf(scale[3 i + k])                                                           (a NaN wins, as torch.max)
+ *     big  = m > (float)dense_percent * extent[0]
+ *     low  = 1 / (1 + expf(-opacity[i])) < (float)opacity_min
+ *   with prune_big != 0 (otherwise all three are false):
+ *     wide       = m > 0.1f * extent[0]
+ *     wide_child = max_k expf(logf(expf(scale[3 i + k]) / (float)(0.8 * split_factor))) > 0.1f * extent[0]
+ *     screen     = radius_max != NULL && radius_max[i] > (float)screen_size_max
+ * (radius_max = NULL reproduces the reference, whose screen-space test reads statistics that densify() has just zeroed.)
+ *     EXA_RASTER_DENSIFY_KEEP   the original survives          !(hot && big) && !low && !wide && !screen
+ *     EXA_RASTER_DENSIFY_CLONE  a copy of it survives          hot && !big && !low && !wide
+ *     EXA_RASTER_DENSIFY_SPLIT  split_factor children survive  hot && big && !low && !wide_child
+ *     EXA_RASTER_DENSIFY_CAND   a split candidate              hot && big         (the reference draws noise for it)
+ * With mask != NULL (mask mode, prune_points) the code of row i is KEEP when mask[i] == 0 and 0 otherwise, and none of the
+ * statistics pointers is looked at.
+ *
+ * The workspace ([dev], 16-byte aligned, exa_raster_densify_workspace_size(P0) bytes, every byte the move reads is written
+ * by the plan) begins with the 16-byte record {n_keep, n_clone, n_split, n_cand} (uint32 each) -- the one thing the host
+ * reads back -- followed by one 16-byte record of exclusive offsets per block of EXA_RASTER_DENSIFY_BLOCK rows and one code
+ * byte per row:  size = 16 + 16 * ceil(P0 / BLOCK) + 16 * ceil(P0 / 16).
+ * The scan is one workgroup of EXA_RASTER_DENSIFY_SCAN threads that loops when there are more blocks than threads.
+ *
+ * exa_raster_densify_move takes that workspace, the four totals BY VALUE and n_seg segments (a host array; they travel by
+ * value in the kernel arguments, EXA_RASTER_DENSIFY_MAX_SEGMENTS per launch, more are issued as several launches).  A
+ * segment moves one tensor: src holds P0 rows of row_floats floats, dst has room for dst_rows >= n_out rows,
+ *     n_out = n_keep + n_clone + split_factor * n_split,
+ * and EVERY element of the first n_out rows of dst is written (no zeros_like before the call).  Output row order, the
+ * reference's final order:  surviving originals in source order; surviving clones in source order; copy 0 of every surviving
+ * split row in source order; copy 1 of every one; ...   By role:
+ *     EXA_RASTER_DENSIFY_COPY    every output row is its source row, bit for bit
+ *     EXA_RASTER_DENSIFY_STATE   surviving originals keep their row; every new row is +0.0 (optimizer moments, statistics)
+ *     EXA_RASTER_DENSIFY_SCALE   as COPY for originals and clones; a child's element is logf(expf(s) / (float)(0.8 * split_factor))
+ *     EXA_RASTER_DENSIFY_MEAN    (row_floats = 3) as COPY for originals and clones; copy c of the k-th split CANDIDATE
+ *                                (k counts candidates in source order, surviving or not) is
+ *                                    n_j = noise[3 (c * n_cand + k) + j] * expf(scale[3 i + j])
+ *                                    out_r = ((R_r0 * n_0 + R_r1 * n_1) + R_r2 * n_2) + mean[3 i + r]
+ *                                with R = rotation_6d_to_matrix(rotation[6 i ..]) (csrc/rot6d.h: rows b1, b2, b3) -- the
+ *                                reference's draw order (module.py:196-201), so the result can be compared with it row for
+ *                                row on the same noise.  `rotation` [P0, 6], `scale` [P0, 3] and `noise`
+ *                                [split_factor * n_cand, 3] are the call's; they are needed only for MEAN segments.
+ * A workgroup owns one block of source rows, rebuilds the compact lists of its kept, cloned and split rows in LDS (ballot
+ * and popcount) and walks its slice of every output range as a flat run of floats.  All accesses are 4 bytes wide and need
+ * 4-byte alignment only.  A workgroup that finds other totals in the workspace's record than the call's stores nothing.
+ * No global atomics, no memset, no allocation, no synchronisation, no state: the same inputs give the same bits.
+ *
+ * Checked on the host before any launch: a NULL pointer that the call would read or write: EXA_RASTER_E_NULLPTR; a negative
+ * size or total, totals beyond P0 or n_split > n_cand, split_factor outside 1..8, row_floats < 1, a MEAN segment with
+ * row_floats != 3, an unknown role, dst_rows < n_out: EXA_RASTER_E_INVALID; workspace_bytes below the size query, or a
+ * workspace that is not 16-byte aligned: EXA_RASTER_E_WORKSPACE; a dst range that overlaps a src range, another dst range,
+ * the workspace or one of rotation / scale / noise: EXA_RASTER_E_ALIAS.  P0 = 0 (and, for the move, n_seg = 0): returns 0
+ * without a launch.
+ */
+#define EXA_RASTER_DENSIFY_MAX_SEGMENTS 64
+#define EXA_RASTER_DENSIFY_BLOCK 256        /* source rows per workgroup */
+#define EXA_RASTER_DENSIFY_SCAN 256         /* count records per round of the scan */
+#define EXA_RASTER_DENSIFY_KEEP 1
+#define EXA_RASTER_DENSIFY_CLONE 2
+#define EXA_RASTER_DENSIFY_SPLIT 4
+#define EXA_RASTER_DENSIFY_CAND 8
+#define EXA_RASTER_DENSIFY_COPY 0
+#define EXA_RASTER_DENSIFY_STATE 1
+#define EXA_RASTER_DENSIFY_MEAN 2
+#define EXA_RASTER_DENSIFY_SCALE 3
+typedef struct ExaRasterDensifySegment {
+    const float* src;                       /* [dev] P0 rows of row_floats floats */
+    float* dst;                             /* [dev] dst_rows rows of row_floats floats; the first n_out are written */
+    int64_t row_floats;
+    int64_t dst_rows;
+    int32_t role;                           /* EXA_RASTER_DENSIFY_COPY / _STATE / _MEAN / _SCALE */
+    int32_t reserved;
+} ExaRasterDensifySegment;
+int exa_raster_densify_workspace_size(int32_t P0, uint64_t* bytes);
+int exa_raster_densify_plan(int32_t P0, const float* grad_accum, const float* track_cnt, const float* scale,
+                            const float* opacity, const float* radius_max, const float* extent, const uint8_t* mask,
+                            double grad_thr, double dense_percent, double opacity_min, int32_t prune_big,
+                            int32_t split_factor, double screen_size_max, void* workspace, uint64_t workspace_bytes,
+                            void* stream);
+int exa_raster_densify_move(int32_t P0, int32_t split_factor, const void* workspace, uint64_t workspace_bytes,
+                            int32_t n_keep, int32_t n_clone, int32_t n_split, int32_t n_cand,
+                            const ExaRasterDensifySegment* segs, int32_t n_seg, const float* rotation, const float* scale,
+                            const float* noise, void* stream);
 
 /*
  * Optional per-kernel timing for benchmarks (the only state the library ever keeps, process-wide,
