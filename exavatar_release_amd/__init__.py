@@ -90,6 +90,12 @@ six parameters and their Adam moments, one host synchronisation; reference ``ava
 called at ``avatar/main/model.py:279-292``):
 
     from exavatar_release_amd import SceneGaussian, densify_plan, densify_apply, prune_plan
+
+and for the perceptual term of the loss block (``LPIPS``: ``lpips.LPIPS(net='vgg')`` behind the bbox crop, forward and the
+gradient w.r.t. the render, without the ``lpips`` and ``torchvision`` packages; reference ``avatar/common/nets/loss.py:77-95``,
+called at ``avatar/main/model.py:199,206``):
+
+    from exavatar_release_amd import LPIPS, lpips_distance
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -114,6 +120,7 @@ from .posed_body import PosedBody, PosedBodyOutput
 from .face_loss import FaceRGBLoss, face_composite, foreground_composite
 from .optim import Adam, adam_step
 from .scene_gaussian import SceneGaussian
+from .lpips import LPIPS, lpips_distance
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -125,4 +132,4 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
            'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step',
-           'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan']
+           'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance']

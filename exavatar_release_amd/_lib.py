@@ -274,6 +274,18 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
                              [ctypes.c_int64] + [c_void_p] * 3),
     'exa_composite_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 4 + [ctypes.c_float, c_void_p]),
     'exa_composite_backward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 6),
+    # LPIPS (csrc/lpips.hip); shift_scale, weights, biases, head_grads, partials and npix are host arrays
+    'exa_lpips_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, _U64P]),
+    'exa_lpips_tap_layout': (ctypes.c_int, [_I32, _I32, _I32, _I32, _U64P, _IP]),
+    'exa_lpips_trunk_forward': (ctypes.c_int, [_I32, _I32, _I32, _IP, c_void_p, ctypes.POINTER(ctypes.c_float), _PP, _PP,
+                                               c_void_p, _U64, c_void_p]),
+    'exa_lpips_trunk_backward': (ctypes.c_int, [_I32, _I32, _I32, _IP, ctypes.POINTER(ctypes.c_float), _PP, _PP, c_void_p,
+                                                _U64, c_void_p, c_void_p]),
+    'exa_lpips_normalize': (ctypes.c_int, [ctypes.c_int64, _I32, c_void_p, c_void_p, c_void_p]),
+    'exa_lpips_head_blocks': (ctypes.c_int64, [ctypes.c_int64]),
+    'exa_lpips_head_forward': (ctypes.c_int, [_I32, ctypes.c_int64, _I32] + [c_void_p] * 6),
+    'exa_lpips_head_reduce': (ctypes.c_int, [_I32, _I32, _PP, ctypes.POINTER(ctypes.c_int64), c_void_p, c_void_p]),
+    'exa_lpips_head_backward': (ctypes.c_int, [_I32, ctypes.c_int64, _I32] + [c_void_p] * 6),
     # the Adam step (csrc/adam.hip); `segs` is a host array
     'exa_raster_adam_step': (ctypes.c_int, [ctypes.POINTER(ExaRasterAdamSegment), _I32, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, c_void_p]),
@@ -429,6 +441,10 @@ def sizes_query(abi, name, struct, *args):
 
 def skin_workspace_size(V, J):
     return size_query(SKIN, 'exa_skin_workspace_size', V, J)
+
+
+def lpips_workspace_size(B, h, w):
+    return size_query(RASTER, 'exa_lpips_workspace_size', B, h, w)
 
 
 def densify_workspace_size(P0):

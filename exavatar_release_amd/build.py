@@ -63,6 +63,8 @@ SOURCES = {
     'pose_params.hip': ['-ffp-contract=off'],
     # the face-composited L1 term and the composites are defined operation by operation (include/exa_raster.h)
     'face_loss.hip': ['-ffp-contract=off'],
+    # LPIPS: the input map, the head and every sum order are defined operation by operation (include/exa_raster.h)
+    'lpips.hip': ['-ffp-contract=off'],
     # the Adam step is defined operation by operation (include/exa_raster.h)
     'adam.hip': ['-ffp-contract=off'],
     # the densification's decisions and children are defined operation by operation (include/exa_raster.h)

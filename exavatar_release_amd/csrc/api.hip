@@ -857,6 +857,127 @@ int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const flo
     return 0;
 }
 
+// B images, a crop of h x w: the sizes the LPIPS kernels index with 32 bits
+static int check_lpips_sizes(int32_t B, int32_t h, int32_t w) {
+    if (B < 0 || h < 0 || w < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (B > 0 && (h < EXA_LPIPS_MIN_CROP || w < EXA_LPIPS_MIN_CROP))
+        return fail(EXA_RASTER_E_INVALID, "lpips: the crop is smaller than 16 x 16 (the fifth tap would be empty)");
+    if (B > 65535 || (int64_t)B * h * w > 0x7fffffffLL / 16)
+        return fail(EXA_RASTER_E_INVALID, "lpips: more than 65535 images or 2^27 - 1 crop pixels");
+    return 0;
+}
+
+static int check_lpips_trunk(int32_t B, int32_t H, int32_t W, const int32_t* crop, uint64_t ws_bytes) {
+    int rc = check_crop(B, 3, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * H * W > 0x7fffffffLL) return fail(EXA_RASTER_E_INVALID, "lpips: more than 2^31 - 1 image pixels");
+    if ((rc = check_lpips_sizes(B, crop[3], crop[2]))) return rc;
+    if (ws_bytes < lpips_workspace_floats(B, crop[3], crop[2]) * sizeof(float))
+        return fail(EXA_RASTER_E_INVALID, "lpips: the workspace is smaller than exa_lpips_workspace_size()");
+    return 0;
+}
+
+int exa_lpips_workspace_size(int32_t B, int32_t h, int32_t w, uint64_t* bytes) {
+    if (!bytes) return fail(EXA_RASTER_E_NULLPTR, "lpips: bytes is NULL");
+    if (int rc = check_lpips_sizes(B, h, w)) return rc;
+    *bytes = lpips_workspace_floats(B, h, w) * sizeof(float);
+    return 0;
+}
+
+int exa_lpips_tap_layout(int32_t B, int32_t h, int32_t w, int32_t tap, uint64_t* byte_offset, int32_t* shape) {
+    if (!byte_offset || !shape) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    if (tap < 0 || tap >= EXA_LPIPS_TAPS) return fail(EXA_RASTER_E_INVALID, "lpips: tap must be 0 .. 4");
+    if (int rc = check_lpips_sizes(B, h, w)) return rc;
+    *byte_offset = lpips_tap_offset_floats(B, h, w, tap) * sizeof(float);
+    lpips_tap_shape(h, w, tap, &shape[0], &shape[1], &shape[2]);
+    return 0;
+}
+
+int exa_lpips_trunk_forward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* img,
+                            const float* shift_scale, const float* const* weights, const float* const* biases, void* ws,
+                            uint64_t ws_bytes, void* stream) {
+    if (int rc = check_lpips_trunk(B, H, W, crop, ws_bytes)) return rc;
+    if (B == 0) return 0;
+    if (!img || !shift_scale || !weights || !biases || !ws) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    for (int l = 0; l < EXA_LPIPS_LAYERS; ++l)
+        if (!weights[l] || !biases[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL weight or bias");
+    for (int c = 3; c < 6; ++c)
+        if (!(shift_scale[c] != 0.0f)) return fail(EXA_RASTER_E_INVALID, "lpips: a scale of the input map is 0 or NaN");
+    EXA_HIP(launch_lpips_trunk_fwd(B, H, W, crop, img, shift_scale, weights, biases, static_cast<float*>(ws),
+                                   static_cast<hipStream_t>(stream)), "lpips_trunk_fwd");
+    return 0;
+}
+
+int exa_lpips_trunk_backward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* shift_scale,
+                             const float* const* weights_t, const float* const* head_grads, void* ws, uint64_t ws_bytes,
+                             float* dL_dimg, void* stream) {
+    if (int rc = check_lpips_trunk(B, H, W, crop, ws_bytes)) return rc;
+    if (B == 0) return 0;
+    if (!shift_scale || !weights_t || !head_grads || !ws || !dL_dimg) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    for (int l = 0; l < EXA_LPIPS_LAYERS; ++l)
+        if (!weights_t[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL weight or bias");
+    for (int t = 0; t < EXA_LPIPS_TAPS; ++t)
+        if (!head_grads[t]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL head gradient");
+    for (int c = 3; c < 6; ++c)
+        if (!(shift_scale[c] != 0.0f)) return fail(EXA_RASTER_E_INVALID, "lpips: a scale of the input map is 0 or NaN");
+    EXA_HIP(launch_lpips_trunk_bwd(B, H, W, crop, shift_scale, weights_t, weights_t[0], head_grads, static_cast<float*>(ws),
+                                   dL_dimg, static_cast<hipStream_t>(stream)), "lpips_trunk_bwd");
+    return 0;
+}
+
+// the head's arrays: B images of npix pixels and C channels, indexed with 32 bits per image
+static int check_lpips_head(int32_t B, int64_t npix, int32_t C) {
+    if (B < 0 || npix < 0 || C < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (C % 4 != 0 || C == 0) return fail(EXA_RASTER_E_INVALID, "lpips head: C must be a positive multiple of 4");
+    if (B > 65535 || npix > 0x7fffffffLL - 256)
+        return fail(EXA_RASTER_E_INVALID, "lpips head: more than 65535 images or 2^31 - 257 pixels per image");
+    return 0;
+}
+
+int exa_lpips_normalize(int64_t N, int32_t C, const float* f, float* out, void* stream) {
+    if (N < 0 || C < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (C % 4 != 0 || C == 0) return fail(EXA_RASTER_E_INVALID, "lpips head: C must be a positive multiple of 4");
+    if (N > 0x7fffffffLL * 256) return fail(EXA_RASTER_E_INVALID, "lpips head: more than 2^39 pixels");
+    if (N > 0 && (!f || !out)) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    EXA_HIP(launch_lpips_normalize(N, C, f, out, static_cast<hipStream_t>(stream)), "lpips_normalize");
+    return 0;
+}
+
+int64_t exa_lpips_head_blocks(int64_t npix) { return npix <= 0 ? 0 : lpips_head_blocks(npix); }
+
+int exa_lpips_head_forward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                           float* d_map, float* partials, void* stream) {
+    if (int rc = check_lpips_head(B, npix, C)) return rc;
+    if ((int64_t)B * npix > 0 && (!f_out || !n_target || !lin || !partials))
+        return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    EXA_HIP(launch_lpips_head_fwd(B, npix, C, f_out, n_target, lin, d_map, partials, static_cast<hipStream_t>(stream)),
+            "lpips_head_fwd");
+    return 0;
+}
+
+int exa_lpips_head_reduce(int32_t B, int32_t n_taps, const float* const* partials, const int64_t* npix, float* out,
+                          void* stream) {
+    if (B < 0 || B > 65535) return fail(EXA_RASTER_E_INVALID, "lpips head: B must be 0 .. 65535");
+    if (n_taps < 1 || n_taps > EXA_LPIPS_MAX_TAPS) return fail(EXA_RASTER_E_INVALID, "lpips head: n_taps must be 1 .. 8");
+    if (!partials || !npix || (B > 0 && !out)) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    for (int l = 0; l < n_taps; ++l) {
+        if (npix[l] <= 0 || npix[l] > 0x7fffffffLL - 256) return fail(EXA_RASTER_E_INVALID, "lpips head: a tap without pixels");
+        if (B > 0 && !partials[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    }
+    EXA_HIP(launch_lpips_head_reduce(B, n_taps, partials, npix, out, static_cast<hipStream_t>(stream)), "lpips_head_reduce");
+    return 0;
+}
+
+int exa_lpips_head_backward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                            const float* dL_dout, float* dL_df, void* stream) {
+    if (int rc = check_lpips_head(B, npix, C)) return rc;
+    if ((int64_t)B * npix > 0 && (!f_out || !n_target || !lin || !dL_dout || !dL_df))
+        return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    EXA_HIP(launch_lpips_head_bwd(B, npix, C, f_out, n_target, lin, dL_dout, dL_df, static_cast<hipStream_t>(stream)),
+            "lpips_head_bwd");
+    return 0;
+}
+
 int exa_raster_adam_step(const ExaRasterAdamSegment* segs, int32_t n_seg, double beta1, double beta2, double eps,
                          void* stream) {
     if (n_seg < 0) return fail(EXA_RASTER_E_INVALID, "adam: negative n_seg");

@@ -591,6 +591,23 @@ hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, 
                            float* d_face, hipStream_t s);
 hipError_t launch_composite_fwd(int mode, int B, int C, int H, int W, const float* a, const float* sel, const float* b,
                                 float* out, float thr, hipStream_t s);
+// lpips.hip: the LPIPS (VGG-16) trunk both ways and the head (sizes, the window and the pointers are the caller's to
+// check).  The workspace is carved by lpips.hip alone; offsets and sizes are in floats.
+uint64_t lpips_workspace_floats(int B, int h, int w);
+uint64_t lpips_tap_offset_floats(int B, int h, int w, int tap);
+void lpips_tap_shape(int h, int w, int tap, int* th, int* tw, int* tc);
+int64_t lpips_head_blocks(int64_t npix);
+hipError_t launch_lpips_trunk_fwd(int B, int H, int W, const int* crop, const float* img, const float* shift_scale,
+                                  const float* const* wpk, const float* const* bias, float* ws, hipStream_t s);
+hipError_t launch_lpips_trunk_bwd(int B, int H, int W, const int* crop, const float* shift_scale, const float* const* wpk_t,
+                                  const float* w1, const float* const* head_grads, float* ws, float* dimg, hipStream_t s);
+hipError_t launch_lpips_normalize(int64_t N, int C, const float* f, float* out, hipStream_t s);
+hipError_t launch_lpips_head_fwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w, float* dmap,
+                                 float* partials, hipStream_t s);
+hipError_t launch_lpips_head_reduce(int B, int n_taps, const float* const* partials, const int64_t* npix, float* out,
+                                    hipStream_t s);
+hipError_t launch_lpips_head_bwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w,
+                                 const float* gout, float* dfo, hipStream_t s);
 // adam.hip: the Adam step of up to ADAM_MAX_SEGMENTS non-empty tensors, the kernel's argument block as the caller fills it
 // (everything in it is the caller's to check)
 constexpr int ADAM_MAX_SEGMENTS = 64;

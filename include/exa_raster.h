@@ -552,6 +552,79 @@ int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const flo
                            const float* dL_dout, float* dL_dimg, float* dL_dface, void* stream);
 
 /*
+ * LPIPS with the VGG-16 trunk (csrc/lpips.hip): lpips.LPIPS(net='vgg') 0.1.4 in eval mode behind the reference's wrapper
+ * (avatar/common/nets/loss.py:77-95), forward and the gradient w.r.t. the first image.  fp32 throughout; fused multiply-adds
+ * only where written (fmaf, or the MFMA, which is bit-equal to an fmaf chain).
+ *
+ * Arrays.  img, dL_dimg: [B, 3, H, W].  crop = {x0, y0, w, h}, the clamped bbox, w >= 16 and h >= 16.  Every activation,
+ * tap, head gradient and feature array is CHANNEL-INNERMOST: [B, rows, columns, C].  Block b = 0 .. 4 of the trunk works at
+ * (h >> b) x (w >> b); the 13 layers have Cin 3, 64 | 64, 128 | 128, 256, 256 | 256, 512, 512 | 512, 512, 512 and
+ * Cout 64, 64 | 128, 128 | 256, 256, 256 | 512, 512, 512 | 512, 512, 512; tap t is the output of layer 1, 3, 6, 9, 12
+ * (counting from 0) with C = 64, 128, 256, 512, 512.
+ * shift_scale: HOST array {shift_r, shift_g, shift_b, scale_r, scale_g, scale_b}.
+ * weights, biases, weights_t, head_grads, partials (of the reduce): HOST arrays of device pointers.
+ *   weights[0] = weights_t[0]: the first layer as [tap = 3 ky + kx][ci][co] (27 x 64 floats).
+ *   weights[l], l >= 1: layer l's [Cout, Cin, 3, 3] as [Cout / 64][Cin / 16][tap][g = 0, 1][co = 0 .. 63][p = 0 .. 7], the
+ *     element at p being input channel 16 chunk + 8 g + 2 (p & 3) + (p >> 2).
+ *   weights_t[l], l >= 1: the same image of the TRANSPOSED and 180-degree ROTATED weights wt[ci, co, ky, kx] =
+ *     w[co, ci, 2 - ky, 2 - kx] (so its Cout is the layer's Cin).
+ * Workspace: exa_lpips_workspace_size() bytes ([dev], 256-byte aligned), carved by the library: the 13 activations, the
+ * mapped input and two gradient buffers of B h w 64 floats; (270 + 3 + 128) B h w floats but for rounding.  The forward
+ * writes every section before it is read; the backward reads the activations its forward left there.
+ * exa_lpips_tap_layout() gives tap t's byte offset in it and shape = {rows, columns, C}.
+ *
+ * exa_lpips_trunk_forward.  Input map per crop pixel and channel: x = ((img * 2 - 1) - shift) / scale, one rounding per
+ *   operation.  Convolution (3 x 3, stride 1, zero padding 1 at the border of the CROP) per output element: per chunk of
+ *   16 input channels a chain c = 0; c = fma(in, w, c) over the chunk's 144 terms, the taps (ky, kx) row-major and inside a
+ *   tap the chunk's channels ascending; s = 0, then s = s + c over the chunks ascending (the first layer: one chain, taps
+ *   row-major, its 3 channels ascending, taps in the padding skipped).  The order is a property of the shape alone; a
+ *   single K-term chain would carry the rounding of K = 4608 additions at the deep layers.  Then out = max(s + bias, 0).  The 2 x 2 stride-2 max-pool (floor) in front of
+ *   blocks 1 .. 4 is taken when the next layer reads its input; pooled arrays are never stored.
+ * exa_lpips_normalize: out = f / (sqrt(S) + 1e-10) per pixel of f [N, C], C % 4 == 0, with S = sum_c f_c^2 as four running
+ *   sums s_k over the channels c = k (mod 4) ascending, s_k = s_k + f_c * f_c, then (s_0 + s_1) + (s_2 + s_3).
+ * exa_lpips_head_forward (one tap; grid of exa_lpips_head_blocks(npix) = ceil(npix / 256) workgroups per image): per pixel
+ *   e_c = f_out_c / (sqrt(S) + 1e-10) - n_target_c; d = sum_c lin_c * (e_c * e_c) in S's order; d_map [B, npix] (or NULL)
+ *   receives d; partials [B, blocks] receives the workgroup's sum of d: the wave butterfly over lane distances 32 .. 1, then
+ *   ((wave 0 + wave 1) + wave 2) + wave 3, as exa_face_l1_forward.
+ * exa_lpips_head_reduce: one workgroup per image.  Per tap l = 0 .. n_taps - 1 (n_taps <= EXA_LPIPS_MAX_TAPS): thread j adds
+ *   the image's partials j, j + 256, .. in that order, then the workgroup sum, D_l = sum / (float)npix[l]; out[b] =
+ *   (((D_0 + D_1) + D_2) + ..).  No atomics: the same bits on every call.
+ * exa_lpips_head_backward (one tap): with g = dL_dout[b] * (1 / (float)npix), r = sqrt(S), u_c = ((2 lin_c) e_c) g and
+ *   dot = sum_c u_c * f_out_c (S's order): dL_df_c = u_c / (r + 1e-10) - f_out_c * (dot / (r * (r + 1e-10)^2)); where r = 0 the
+ *   second term is 0 (torch's sqrt backward gives NaN there: the library's "finite gradient at zero rows" rule).
+ * exa_lpips_trunk_backward: head_grads[t] = dL/d(tap t) as exa_lpips_head_backward leaves it.  The gradient of an
+ *   activation a of layer l - 1 is the convolution of layer l's (masked) gradient with weights_t[l] in the order above
+ *   (Cin and Cout swapped); through a pool it goes to the first maximum of the 2 x 2 window in row-major order and the
+ *   row / column an odd size drops gets 0; the head's gradient is added at a tap; then it is multiplied by [a > 0].  The
+ *   first layer: per crop pixel and input channel s = 0; taps row-major, the 64 output channels ascending,
+ *   s = fma(g[y - ky + 1][x - kx + 1][co], w[tap][ci][co], s); dL_dimg = (s / scale) * 2.  dL_dimg is written WHOLE by that
+ *   kernel, zeros outside the crop: the caller clears nothing.
+ * Errors before any device call: negative sizes, a window outside the image or below 16 x 16, a short workspace, C not a
+ * multiple of 4, a zero scale: EXA_RASTER_E_INVALID; a missing array: EXA_RASTER_E_NULLPTR.  The calls neither allocate nor
+ * synchronise; B = 0 is a no-op.
+ */
+#define EXA_LPIPS_LAYERS 13
+#define EXA_LPIPS_TAPS 5
+#define EXA_LPIPS_MAX_TAPS 8
+#define EXA_LPIPS_MIN_CROP 16
+int exa_lpips_workspace_size(int32_t B, int32_t h, int32_t w, uint64_t* bytes);
+int exa_lpips_tap_layout(int32_t B, int32_t h, int32_t w, int32_t tap, uint64_t* byte_offset, int32_t* shape);
+int exa_lpips_trunk_forward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* img,
+                            const float* shift_scale, const float* const* weights, const float* const* biases, void* ws,
+                            uint64_t ws_bytes, void* stream);
+int exa_lpips_trunk_backward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* shift_scale,
+                             const float* const* weights_t, const float* const* head_grads, void* ws, uint64_t ws_bytes,
+                             float* dL_dimg, void* stream);
+int exa_lpips_normalize(int64_t N, int32_t C, const float* f, float* out, void* stream);
+int64_t exa_lpips_head_blocks(int64_t npix);
+int exa_lpips_head_forward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                           float* d_map, float* partials, void* stream);
+int exa_lpips_head_reduce(int32_t B, int32_t n_taps, const float* const* partials, const int64_t* npix, float* out,
+                          void* stream);
+int exa_lpips_head_backward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                            const float* dL_dout, float* dL_df, void* stream);
+
+/*
  * The Adam step (csrc/adam.hip): `trainer.optimizer.step()` of the reference (avatar/main/train.py:57, base.py:83-85:
  * torch.optim.Adam without weight decay or amsgrad) for any number of separately allocated tensors, one launch per
  * EXA_RASTER_ADAM_MAX_SEGMENTS of them.  A native host applies the gradients of exa_raster_backward with it.
