@@ -248,6 +248,7 @@ RASTER = Abi('exa_raster', 'exa_raster.h', 139, {
     'exa_raster_read_header_full_async': (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),
     'exa_raster_host_device_pointer': (ctypes.c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
     'exa_raster_header_status': (ctypes.c_int, [ctypes.POINTER(ExaRasterHeader)]),
+    'exa_raster_launch_paths': (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_uint32)]),
     'exa_raster_camera_block': (ctypes.c_int, [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p,
                                                c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p,
                                                ctypes.c_uint32, c_void_p]),
@@ -473,6 +474,20 @@ def mesh_workspace_sizes(N, F, H, W):
 
 def workspace_sizes(P, W, H, capacity):
     return sizes_query(RASTER, 'exa_raster_workspace_sizes', ExaRasterWorkspaceSizes, P, W, H, capacity)
+
+
+# bits of exa_raster_launch_paths (include/exa_raster.h)
+PATH_SCANS_MERGED, PATH_WALK_TWO_CELLS, PATH_MASK_READY, PATH_MULTI_PART, PATH_SPLIT_SORT = 1, 2, 4, 8, 16
+PATH_COMPOSE_TRIPS_SHIFT = 16
+PATH_NAMES = {PATH_SCANS_MERGED: 'SCANS_MERGED', PATH_WALK_TWO_CELLS: 'WALK_TWO_CELLS', PATH_MASK_READY: 'MASK_READY',
+              PATH_MULTI_PART: 'MULTI_PART', PATH_SPLIT_SORT: 'SPLIT_SORT'}
+
+
+def launch_paths(W, H, P, fused=True):
+    """(set of path names, compose-scan trips) a W x H render of P Gaussians takes: exa_raster_launch_paths, host only."""
+    bits = ctypes.c_uint32()
+    check(load().exa_raster_launch_paths(W, H, P, int(bool(fused)), ctypes.byref(bits)))
+    return ({n for b, n in PATH_NAMES.items() if bits.value & b}, bits.value >> PATH_COMPOSE_TRIPS_SHIFT)
 
 
 def timing_enable(on):

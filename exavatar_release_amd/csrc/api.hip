@@ -116,6 +116,26 @@ int exa_raster_workspace_sizes(int32_t P, int32_t W, int32_t H, uint64_t capacit
     return 0;
 }
 
+// Which launches a render of this size takes, from the predicates the launchers themselves ask (common.h): no device call.
+int exa_raster_launch_paths(int32_t width, int32_t height, int32_t P, int32_t fused, uint32_t* bits_out) {
+    if (!bits_out) return fail(EXA_RASTER_E_NULLPTR, "bits_out is NULL");
+    if (width < 0 || height < 0 || P < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (P > (1 << 26) - 4) return fail(EXA_RASTER_E_INVALID, "more than 2^26 - 4 Gaussians (32-bit byte offsets of the 64-byte splat records)");
+    const Grid g = make_grid(width, height);
+    if (g.cells > MAX_CELLS || width > 32768 || height > 32768)
+        return fail(EXA_RASTER_E_INVALID, "image too large (more than 4096 cells of 64x64 pixels)");
+    uint32_t bits = 0;
+    const bool merged = fused != 0 && merge_scans_at(g.cells, num_chunks(P));
+    if (merged) bits |= EXA_RASTER_PATH_SCANS_MERGED;
+    if (merged && walk_two_cells(g.cells)) bits |= EXA_RASTER_PATH_WALK_TWO_CELLS;
+    if (g.cells > 0 && mask_ready_entries(g.cells)) bits |= EXA_RASTER_PATH_MASK_READY;
+    if (g.cells > 0 && multi_part_binning(g.cells)) bits |= EXA_RASTER_PATH_MULTI_PART;
+    if (g.subtiles > 0 && split_sort(g.subtiles)) bits |= EXA_RASTER_PATH_SPLIT_SORT;
+    bits |= (uint32_t)compose_scan_trips(g.cells) << EXA_RASTER_PATH_COMPOSE_TRIPS_SHIFT;
+    *bits_out = bits;
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {
@@ -157,9 +177,7 @@ BinArgs bin_args(const ExaRasterForwardJob& j) {
 bool can_merge_scans(const ExaRasterForwardJob* jobs, int K) {
     for (int k = 0; k < K; ++k) {
         const int cells = make_grid(jobs[k].settings->image_width, jobs[k].settings->image_height).cells;
-        const int chunks = num_chunks(jobs[k].P);
-        if (cells == 0 || cells > MERGE_MAX_CELLS || chunks > MERGE_MAX_CHUNKS || (int64_t)cells * chunks > MERGE_MAX_MATRIX)
-            return false;
+        if (!merge_scans_at(cells, num_chunks(jobs[k].P))) return false;
     }
     return true;
 }

@@ -445,7 +445,7 @@ __global__ __launch_bounds__(SC_BLOCK) void cell_scatter_kernel(Batch<BinArgs> b
         for (int c = tid; c < cells; c += SC_BLOCK) { s_tot[c] = 0ull; s_bef[c] = 0ull; }
         __syncthreads();
         {
-            if ((cells & 1) == 0) {                             // two cells per thread and row: 16-byte loads, twice the row groups
+            if (walk_two_cells(cells)) {                        // two cells per thread and row: 16-byte loads, twice the row groups
                 const int cp = cells >> 1, G2 = SC_BLOCK / cp;   // (5.2 -> 4.0 us of this kernel's 13.9 on C3; four cells per thread: the
                                                                  //  same; ten rows in flight: 5.1; rows packed to u32 `inst << 11 | entries`: 5.5)
                 const int c2 = tid % cp, q = tid / cp;
@@ -897,21 +897,7 @@ hipError_t launch_cell_scan(const BinArgs* a, int K, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Which launches of a batch (cells = the largest cell count of its jobs) take the multi-part sub-tile binning, and which of
-// those hand over MASK-READY entries (cell_scatter_kernel<true> -> subtile_count_kernel<.., true>): the footprint test on,
-// and the staged rows of a chunk (40 bytes per Gaussian + the scans' scratch) next to the per-cell arrays within the 64 KB
-// of LDS a workgroup may have.  Both launchers ask here, so that producer and consumer of the entries always agree.
-#ifndef EXA_MASK_READY
-#define EXA_MASK_READY 1                // 0 (build-time, tools/build_variant.sh): masks by subtile_count_kernel, as before
-#endif
-constexpr size_t SCATTER_STAGE_LDS = (size_t)SC_BLOCK * 40 + 512;
-static bool multi_part_binning(int cells) {
-    return !(cells >= dev_knobs().single_cells || cells > 1024);  // (the part table maps one thread to one cell)
-}
-static bool mask_ready_entries(int cells) {
-    return EXA_MASK_READY && dev_knobs().footprint && multi_part_binning(cells) && (size_t)cells * 24 + SCATTER_STAGE_LDS <= 65536;
-}
-
+// (multi_part_binning / mask_ready_entries: common.h, next to the other size predicates)
 hipError_t launch_cell_scatter(const BinArgs* a, int K, hipStream_t s) {
     const Batch<BinArgs> b = make_batch(a, K);
     int chunks = 0, cells = 0;

@@ -556,6 +556,36 @@ struct DevKnobs {
     int split_subtiles;      // EXA_SORT_SPLIT_SUBTILES=<n>: images with at least n sub-tiles sort short lists in their own launch
 };
 const DevKnobs& dev_knobs();
+
+// Which launches a render of a given size takes: the ONE place that says so.  The launchers (api.hip, binning.hip, render_fwd.hip,
+// compose.hip) and the host-only query exa_raster_launch_paths (api.hip) all ask these predicates, so a test that pins a case to
+// a path notices when a constant moves the path away from it (tests/size_cases.py).
+// The scans of the count matrix inside cell_scatter_kernel (fused stage 1 + 2 calls only: MERGE_MAX_* above).
+inline bool merge_scans_at(int cells, int chunks) {
+    return !(cells == 0 || cells > MERGE_MAX_CELLS || chunks > MERGE_MAX_CHUNKS || (int64_t)cells * chunks > MERGE_MAX_MATRIX);
+}
+// The merged column walk of cell_scatter_kernel: two cells per thread (16-byte loads) for even cell counts, one for odd ones.
+__host__ __device__ inline bool walk_two_cells(int cells) { return (cells & 1) == 0; }
+// Which launches of a batch (cells = the largest cell count of its jobs) take the multi-part sub-tile binning, and which of
+// those hand over MASK-READY entries (cell_scatter_kernel<true> -> subtile_count_kernel<.., true>): the footprint test on,
+// and the staged rows of a chunk (40 bytes per Gaussian + the scans' scratch) next to the per-cell arrays within the 64 KB
+// of LDS a workgroup may have.  Both launchers ask here, so that producer and consumer of the entries always agree.
+#ifndef EXA_MASK_READY
+#define EXA_MASK_READY 1                // 0 (build-time, tools/build_variant.sh): masks by subtile_count_kernel, as before
+#endif
+constexpr size_t SCATTER_STAGE_LDS = (size_t)CHUNK * 40 + 512;   // (cell_scatter_kernel: one Gaussian per thread, CHUNK threads)
+constexpr size_t MASK_READY_LDS = 65536;
+inline bool multi_part_binning(int cells) {
+    return !(cells >= dev_knobs().single_cells || cells > 1024);  // (the part table maps one thread to one cell)
+}
+inline bool mask_ready_entries(int cells) {
+    return EXA_MASK_READY && dev_knobs().footprint && multi_part_binning(cells) && (size_t)cells * 24 + SCATTER_STAGE_LDS <= MASK_READY_LDS;
+}
+// The short lists of a large image are sorted by a launch of their own (render_fwd.hip, launch_sort_subtiles).
+inline bool split_sort(int subtiles) { return subtiles >= dev_knobs().split_subtiles; }
+// compose_kernel scans the sub-tile ranges in trips of this many cells, with a carry from trip to trip (compose.hip).
+constexpr int COMPOSE_TRIP_CELLS = 256;
+__host__ __device__ inline int compose_scan_trips(int cells) { return (cells + COMPOSE_TRIP_CELLS - 1) / COMPOSE_TRIP_CELLS; }
 hipError_t launch_ssim_fwd(int N, int H, int W, const float* img1, const float* img2, float* map, float* dm_dmu1,
                            float* dm_dE11, float* dm_dE12, hipStream_t s);
 hipError_t launch_ssim_bwd(int N, int H, int W, const float* img1, const float* img2, const float* dL_dmap,

@@ -29,7 +29,8 @@ namespace exa {
 constexpr int CBLOCK = 1024;             // compose_kernel (one workgroup scans every sub-tile: all loads of a thread in flight at once)
 constexpr int MBLOCK = 256;              // merge_kernel: four independent waves
 constexpr int C_ZERO_WGS = 32;
-constexpr int C_PER = 16;                // sub-tiles per thread and trip of the scan
+constexpr int C_PER = COMPOSE_TRIP_CELLS / (CBLOCK / 64);   // sub-tiles per thread and trip of the scan (16)
+static_assert(C_PER * (CBLOCK / 64) == COMPOSE_TRIP_CELLS && COMPOSE_TRIP_CELLS == 4 * 64, "wave 0 scans four cell totals per lane");
 
 __device__ __forceinline__ uint32_t list_slots(uint32_t n) { return n ? (n + BATCH - 1) / BATCH + 1 : 0u; }   // batches + end slot
 
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(CBLOCK) void compose_kernel(Batch<ComposeArgs> batc
     __shared__ uint32_t s_cell[CBLOCK / 64 * C_PER];
     const int cells = subtiles / SUBS_PER_CELL;
     uint32_t carry = 0;
-    for (int cell0 = 0; cell0 < cells; cell0 += CBLOCK / 64 * C_PER) {
+    for (int cell0 = 0; cell0 < cells; cell0 += COMPOSE_TRIP_CELLS) {
         uint32_t len[C_PER], excl[C_PER];
         uint2 x[C_PER], y[C_PER];
 #pragma unroll

@@ -989,11 +989,10 @@ static int max_subtiles(const RenderFwdArgs* a, int K) {
 hipError_t launch_sort_subtiles(const RenderFwdArgs* a, int K, hipStream_t s) {
     const int subtiles = max_subtiles(a, K);
     if (subtiles == 0) return hipSuccess;
-    const int split_at = dev_knobs().split_subtiles;
     bool keep = false;                   // (all jobs of a call share the flag: the binding sets it per call)
     for (int k = 0; k < K; ++k) keep = keep || a[k].keep_sorted_keys != 0;
     const dim3 grid(subtiles + ORDER_WGS, K);
-    if (subtiles >= split_at) {
+    if (split_sort(subtiles)) {
         sort_short_kernel<<<dim3((subtiles + SBLOCK / 64 - 1) / (SBLOCK / 64), K), SBLOCK, 0, s>>>(make_batch(a, K));
         if (keep) sort_subtiles_kernel<true, true><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));
         else sort_subtiles_kernel<true, false><<<grid, SBLOCK, 0, s>>>(make_batch(a, K));

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define EXA_RASTER_VERSION 139          /* 0.1.3.9: exa_raster_densify_workspace_size / _plan / _move and ExaRasterDensifySegment were added under this number, as exa_raster_adam_step was (new functions only: nothing that existed changed, and tests/test_abi.py pins 139); tile_bytes of exa_raster_workspace_sizes grew (launch-order cursors per XCD region, one class code per sub-tile); no signature changed; 0.1.3.8: grad_bytes of exa_raster_workspace_sizes includes the 92 B x P group scratch of summed batches of more than four views; 0.1.3.7: ExaRasterComposeJob.radii_out / is_vis_out; 0.1.3.6: exa_raster_select_row; 0.1.3.5: EXA_RASTER_STAGE_* bits of store_ctx; 0.1.3.4: ExaRasterBackwardJob.used_slots; 0.1.3.3: ExaRasterForwardJob.is_vis, ExaRasterBackwardJob.accumulate; 0.1.3.2: ExaRasterBackwardJob.dL_dcolor_indirect, exa_raster_store_pointers, ExaRasterComposeJob.a_color .. a_bg; 0.1.3.1: composite renders (exa_raster_forward_compose_batch); 0.1.3: header.num_tile_instances, EXA_RASTER_E_OVERFLOW / _E_ALIAS, exa_raster_camera_block,
+#define EXA_RASTER_VERSION 139          /* 0.1.3.9: exa_raster_densify_workspace_size / _plan / _move and ExaRasterDensifySegment were added under this number, as exa_raster_adam_step was (new functions only: nothing that existed changed, and tests/test_abi.py pins 139), and so was the host-only query exa_raster_launch_paths; tile_bytes of exa_raster_workspace_sizes grew (launch-order cursors per XCD region, one class code per sub-tile); no signature changed; 0.1.3.8: grad_bytes of exa_raster_workspace_sizes includes the 92 B x P group scratch of summed batches of more than four views; 0.1.3.7: ExaRasterComposeJob.radii_out / is_vis_out; 0.1.3.6: exa_raster_select_row; 0.1.3.5: EXA_RASTER_STAGE_* bits of store_ctx; 0.1.3.4: ExaRasterBackwardJob.used_slots; 0.1.3.3: ExaRasterForwardJob.is_vis, ExaRasterBackwardJob.accumulate; 0.1.3.2: ExaRasterBackwardJob.dL_dcolor_indirect, exa_raster_store_pointers, ExaRasterComposeJob.a_color .. a_bg; 0.1.3.1: composite renders (exa_raster_forward_compose_batch); 0.1.3: header.num_tile_instances, EXA_RASTER_E_OVERFLOW / _E_ALIAS, exa_raster_camera_block,
                                            exa_raster_header_status; 0.1.2: ExaRasterBackwardJob.grad_first; .1: exa_raster_read_header_async */
 #define EXA_RASTER_TILE 16              /* 16x16 pixel tiles (upstream BLOCK_X/BLOCK_Y) */
 
@@ -300,6 +300,29 @@ typedef struct ExaRasterComposeJob {
 /* tile_bytes / bin_bytes of a composite's workspaces, grad_bytes of its backward scratch (geom_bytes = 0) */
 int exa_raster_compose_sizes(int32_t W, int32_t H, uint64_t capacity, uint64_t capacity_b, ExaRasterWorkspaceSizes* out);
 int exa_raster_forward_compose_batch(const ExaRasterComposeJob* jobs, int32_t K, int32_t store_ctx, void* stream);
+
+/*
+ * Which launches a render of `width` x `height` pixels and P Gaussians takes -- host-only: it launches nothing, needs no
+ * device and reads the developer knobs (EXA_FOOTPRINT, EXA_BIN_SINGLE_CELLS, EXA_SORT_SPLIT_SUBTILES) exactly as the launchers
+ * do, because it asks the very predicates they ask.  `fused` != 0: one call does stage 1 + 2 (exa_raster_forward /
+ * exa_raster_forward_batch); 0: the two-stage protocol (exa_raster_forward_bin, then _render), which never merges the scans.
+ * For a batch every job's size has to allow the merge, and the binning / sort paths follow the largest job.
+ *   SCANS_MERGED    cell_scatter_kernel scans the (chunk, cell) count matrix itself; otherwise col_scan + cell_scan launches
+ *   WALK_TWO_CELLS  that merged scan walks two cells per thread (even cell counts); only ever set with SCANS_MERGED
+ *   MASK_READY      cell_scatter_kernel hands its entries over with their footprint masks; otherwise subtile_count_kernel
+ *                   (or the one-workgroup-per-cell kernel) computes them
+ *   MULTI_PART      sub-tile binning in two launches of several workgroups per cell; otherwise one workgroup per cell
+ *   SPLIT_SORT      the short sub-tile lists are sorted by a launch of their own
+ *   bits 16 .. 31   trips of the composite's range scan over the cells = ceil(cells / 256) (0 for an empty image)
+ * Sizes the render calls refuse (more than 4096 cells, a side above 32768, P above 2^26 - 4) are refused here too.
+ */
+#define EXA_RASTER_PATH_SCANS_MERGED   1u
+#define EXA_RASTER_PATH_WALK_TWO_CELLS 2u
+#define EXA_RASTER_PATH_MASK_READY     4u
+#define EXA_RASTER_PATH_MULTI_PART     8u
+#define EXA_RASTER_PATH_SPLIT_SORT     16u
+#define EXA_RASTER_PATH_COMPOSE_TRIPS_SHIFT 16
+int exa_raster_launch_paths(int32_t width, int32_t height, int32_t P, int32_t fused, uint32_t* bits_out);
 
 /* `store_ctx` of exa_raster_forward_batch / exa_raster_forward_render_batch / exa_raster_forward_compose_batch: bit 0 = keep the
  * backward context (any caller that passes 0 / 1 is unaffected); the two stage bits split one call into two calls with the

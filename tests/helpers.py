@@ -247,3 +247,52 @@ def loss_content(kind, shape, seed=0):
     keep = (base == 0.0) | (base == 1.0)
     keep[..., :, :W // 3] = True                                             # x == y bit for bit
     return torch.where(keep, base, x), base
+
+
+# ---- the five renders of an iteration, three ways (tests/test_gpu_edge_cases.py, tests/test_gpu_size_paths.py)
+def iteration_case(dev, scene, human, refined, H, W, f, bg, seed, cam=None):
+    """render_iteration three ways: merge (composites from the sources' sorted lists), constant prefix (round 2) and the
+    reference's own formulation (five renders of torch.cat((scene.detach(), human)))."""
+    import exavatar_release_amd as exa
+    from exavatar_release_amd import scenes
+    KEYS = ('mean_3d', 'scale', 'rotation', 'opacity', 'rgb')
+    _to = lambda d, dev_: {k: v.to(dev_).requires_grad_(True) for k, v in d.items()}      # noqa: E731
+    cam = cam or scenes.neutral_camera(H, W, focal=f)
+    camd = {k: t.to(dev) for k, t in cam.items()}
+    g = torch.Generator().manual_seed(seed)
+    G = [torch.randn(3, H, W, generator=g).to(dev) for _ in range(5)]
+    Gd = [torch.randn(1, H, W, generator=g).to(dev) for _ in range(5)]
+    rend = exa.GaussianRenderer()
+    res = {}
+    for how in ('merge', 'prefix', 'reference'):
+        s, h, r = _to(scene, dev), _to(human, dev), _to(refined, dev)
+        if how == 'reference':
+            cat = lambda a_, b_: {k: torch.cat((a_[k].detach(), b_[k])) for k in KEYS}      # noqa: E731
+            jobs = [(s, (H, W), camd), (h, (H, W), camd, bg), (cat(s, h), (H, W), camd), (r, (H, W), camd, bg), (cat(s, r), (H, W), camd)]
+            outs = [rend(*j) for j in jobs]
+        else:
+            out = exa.render_iteration(rend, s, h, r, (H, W), camd, bg, merge=(how == 'merge'))
+            outs = [out[k] for k in exa.ITERATION_RENDERS]
+        sum((o['img'] * Gi).sum() + (o['depthmap'] * Gdi).sum() + o['mask'].sum() for o, Gi, Gdi in zip(outs, G, Gd)).backward()
+        torch.cuda.synchronize()
+        m2 = [o['mean_2d'].grad.clone() for o in outs]
+        if how == 'reference':                       # the composites' probes cover cat(scene, human): keep the human rows
+            nS = scene['mean_3d'].shape[0]
+            m2[2], m2[4] = m2[2][nS:], m2[4][nS:]
+        res[how] = dict(imgs=[o[k].detach().clone() for o in outs for k in ('img', 'depthmap', 'mask')],
+                        radii=[o['radius'].clone() for o in outs], m2=m2,
+                        grads=[t[k].grad.clone() for t in (s, h, r) for k in KEYS])
+    return res
+
+
+def assert_iteration_agrees(res):
+    ref = res['reference']
+    for how in ('merge', 'prefix'):
+        got = res[how]
+        for i, (x, y) in enumerate(zip(got['imgs'], ref['imgs'])):
+            assert torch.equal(x, y), '%s image %d' % (how, i)
+        for x, y in zip(got['radii'], ref['radii']):
+            assert torch.equal(x, y)
+        for i, (x, y) in enumerate(zip(got['grads'] + got['m2'], ref['grads'] + ref['m2'])):
+            scale = float(y.abs().max())
+            assert float((x - y).abs().max()) <= 1e-5 * scale + 1e-30, '%s grad %d: %g of %g' % (how, i, float((x - y).abs().max()), scale)

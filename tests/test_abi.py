@@ -18,13 +18,18 @@ INC = os.path.join(ROOT, 'include')
 LIB = os.path.join(ROOT, 'exavatar_release_amd', 'libexa_raster.so')
 
 VERSION = {'exa_raster': 139, 'exa_mesh': 100, 'exa_knn': 100, 'exa_triplane': 100, 'exa_skin': 100, 'exa_mlp': 100}
-MIN_FUNCTIONS = {'exa_raster': 24}
+MIN_FUNCTIONS = {'exa_raster': 25}
 EXACT_FUNCTIONS = {'exa_knn': 5, 'exa_triplane': 5, 'exa_skin': 5}
 
 # Extra C statements of the linked program: host-only calls whose results it prints after the function count and the
 # version, and what they must print.
 PROBES = {
-    'exa_raster': ('  printf(" %s", exa_raster_timing_name(1));\n', ['preprocess_fwd']),
+    # 1080 x 1920: 17 x 30 = 510 cells; 20 000 Gaussians are 20 chunks: merged scans, two-cell walk, mask-ready multi-part
+    # binning, two compose trips; the two-stage protocol (fused = 0) never merges
+    'exa_raster': ('  uint32_t b1 = 0, b0 = 0;\n  int r1 = exa_raster_launch_paths(1080, 1920, 20000, 1, &b1);\n'
+                   '  int r0 = exa_raster_launch_paths(1080, 1920, 20000, 0, &b0);\n'
+                   '  printf(" %s %d %d %u %u", exa_raster_timing_name(1), r1, r0, (unsigned)b1, (unsigned)b0);\n',
+                   ['preprocess_fwd', '0', '0', str((2 << 16) | 15), str((2 << 16) | 12)]),
     # vertex 0: entry 0 (face 0 corner 0); vertex 1: entries 1, 4 (ent[2] = 4); cells 2 x 3, 1 word, 2 meshes -> 48 B -> 256
     'exa_mesh': ('  ExaMeshWorkspaceSizes s;\n  int32_t faces[6] = {0, 1, 2, 2, 1, 3}, off[5], ent[6];\n'
                  '  int rc = exa_mesh_vertex_faces(4, 2, faces, off, ent);\n'

@@ -21,8 +21,8 @@ from exavatar_release_amd import rasterizer as rz
 from exavatar_release_amd import scenes
 from oracle import c_oracle as co
 from oracle import raster_oracle as ro
-from tests.helpers import (IMG_TOL, assert_grads_close, assert_image_close, fuzz_case, gaussians_near_pixels, grad_stats,
-                           image_stats, needle_scene, record_stats, rotation_grad_scale)
+from tests.helpers import (IMG_TOL, assert_grads_close, assert_image_close, assert_iteration_agrees, fuzz_case, gaussians_near_pixels,
+                           grad_stats, image_stats, iteration_case, needle_scene, record_stats, rotation_grad_scale)
 
 pytestmark = pytest.mark.gpu
 
@@ -439,50 +439,7 @@ def test_two_rank_reduced_gradient_equals_single_process_sum(tmp_path):
 
 
 # ---- composite renders: merged lists instead of binning the concatenation -------------------------------------------
-def _iteration_case(dev, scene, human, refined, H, W, f, bg, seed, cam=None):
-    """render_iteration three ways: merge (composites from the sources' sorted lists), constant prefix (round 2) and the
-    reference's own formulation (five renders of torch.cat((scene.detach(), human)))."""
-    cam = cam or scenes.neutral_camera(H, W, focal=f)
-    camd = {k: t.to(dev) for k, t in cam.items()}
-    g = torch.Generator().manual_seed(seed)
-    G = [torch.randn(3, H, W, generator=g).to(dev) for _ in range(5)]
-    Gd = [torch.randn(1, H, W, generator=g).to(dev) for _ in range(5)]
-    rend = exa.GaussianRenderer()
-    res = {}
-    for how in ('merge', 'prefix', 'reference'):
-        s, h, r = _to(scene, dev), _to(human, dev), _to(refined, dev)
-        if how == 'reference':
-            cat = lambda a_, b_: {k: torch.cat((a_[k].detach(), b_[k])) for k in KEYS}      # noqa: E731
-            jobs = [(s, (H, W), camd), (h, (H, W), camd, bg), (cat(s, h), (H, W), camd), (r, (H, W), camd, bg), (cat(s, r), (H, W), camd)]
-            outs = [rend(*j) for j in jobs]
-        else:
-            out = exa.render_iteration(rend, s, h, r, (H, W), camd, bg, merge=(how == 'merge'))
-            outs = [out[k] for k in exa.ITERATION_RENDERS]
-        sum((o['img'] * Gi).sum() + (o['depthmap'] * Gdi).sum() + o['mask'].sum() for o, Gi, Gdi in zip(outs, G, Gd)).backward()
-        torch.cuda.synchronize()
-        m2 = [o['mean_2d'].grad.clone() for o in outs]
-        if how == 'reference':                       # the composites' probes cover cat(scene, human): keep the human rows
-            nS = scene['mean_3d'].shape[0]
-            m2[2], m2[4] = m2[2][nS:], m2[4][nS:]
-        res[how] = dict(imgs=[o[k].detach().clone() for o in outs for k in ('img', 'depthmap', 'mask')],
-                        radii=[o['radius'].clone() for o in outs], m2=m2,
-                        grads=[t[k].grad.clone() for t in (s, h, r) for k in KEYS])
-    return res
-
-
-def _assert_iteration_agrees(res):
-    ref = res['reference']
-    for how in ('merge', 'prefix'):
-        got = res[how]
-        for i, (x, y) in enumerate(zip(got['imgs'], ref['imgs'])):
-            assert torch.equal(x, y), '%s image %d' % (how, i)
-        for x, y in zip(got['radii'], ref['radii']):
-            assert torch.equal(x, y)
-        for i, (x, y) in enumerate(zip(got['grads'] + got['m2'], ref['grads'] + ref['m2'])):
-            scale = float(y.abs().max())
-            assert float((x - y).abs().max()) <= 1e-5 * scale + 1e-30, '%s grad %d: %g of %g' % (how, i, float((x - y).abs().max()), scale)
-
-
+# (iteration_case / assert_iteration_agrees: tests/helpers.py, shared with tests/test_gpu_size_paths.py)
 def test_composite_renders_merge_the_sorted_lists_of_their_sources(dev):
     """exa_raster_forward_compose_batch (csrc/compose.hip): scene + human without binning the concatenation -- the composite
     reuses the sources' splat records and merges their sorted per-sub-tile lists.  Images, depth, alpha and radii equal the
@@ -492,8 +449,8 @@ def test_composite_renders_merge_the_sorted_lists_of_their_sources(dev):
     human = scenes.dist_a_random(1500, H, W, seed=52, focal=f, z_range=(2.0, 4.0))
     refined = {k: (v + 0.01 * torch.randn(v.shape, generator=torch.Generator().manual_seed(53)) if k == 'mean_3d' else v.clone())
                for k, v in human.items()}
-    res = _iteration_case(dev, scene, human, refined, H, W, f, torch.tensor([0.1, 0.2, 0.3], device=dev), 54)
-    _assert_iteration_agrees(res)
+    res = iteration_case(dev, scene, human, refined, H, W, f, torch.tensor([0.1, 0.2, 0.3], device=dev), 54)
+    assert_iteration_agrees(res)
 
 
 def test_composite_renders_depth_ties_long_lists_and_ragged_images(dev):
@@ -517,8 +474,8 @@ def test_composite_renders_depth_ties_long_lists_and_ragged_images(dev):
     scene['scale'][-3:] = torch.tensor([0.6, 0.5, 0.4])                              # splats over every cell
     refined = {k: v.clone() for k, v in human.items()}
     refined['rgb'] = torch.rand(2500, 3, generator=g)
-    res = _iteration_case(dev, scene, human, refined, H, W, f, torch.rand(3, generator=g).to(dev), 74)
-    _assert_iteration_agrees(res)
+    res = iteration_case(dev, scene, human, refined, H, W, f, torch.rand(3, generator=g).to(dev), 74)
+    assert_iteration_agrees(res)
 
 
 def test_composite_copies_the_scene_where_the_human_is_absent(dev):
