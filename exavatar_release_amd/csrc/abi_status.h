@@ -6,8 +6,9 @@
 //   fail(code, what)      "exa_knn: <what>", returns code
 //   fail_hip(e, where)    "exa_knn: HIP error <e> (<text>) in <where>", returns (int)e
 //   launched(kernel)      0, or fail_hip() of hipGetLastError() for the kernel just enqueued
-// An ABI spread over two sources (exa_mesh: mesh_raster.hip and mesh_reg.hip) defines the buffer in one of them and says
-// EXA_ABI_STATUS_SHARED("exa_mesh") in the other, inside the same namespace.
+// An ABI spread over several sources, every stage's entry points next to its kernels, defines the buffer in one of them and
+// says EXA_ABI_STATUS_SHARED(...) in the others, inside the same named namespace: exa_mesh (exa_mesh_impl; the buffer is
+// mesh_raster.hip's) and exa_raster (exa_raster_impl; the buffer is api.hip's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -14,9 +14,21 @@
 //               chunk goes group by group, the last n % 4 elements one by one; a segment with a misaligned array goes
 //               element by element (lane i at element i: still coalesced).  A chunk starts 16 KiB into its arrays, so it
 //               is aligned as its segment is.  No LDS, no barrier, no atomics: the same inputs give the same bits.
-#include "common.h"
+#include <cmath>
+
+#include "../../include/exa_raster.h"
+#include "abi_status.h"
 
 namespace exa {
+
+// the kernel's argument block, as exa_raster_adam_step fills it: up to ADAM_MAX_SEGMENTS non-empty tensors
+constexpr int ADAM_MAX_SEGMENTS = 64;
+struct AdamArgs {
+    int32_t n_seg;                             // 1 .. ADAM_MAX_SEGMENTS, every one with n > 0
+    float w1, b2, w2, eps;                     // (float)(1 - beta1), (float)beta2, (float)(1 - beta2), (float)eps
+    uint32_t start[ADAM_MAX_SEGMENTS + 1];     // first chunk of every segment; start[n_seg] = the grid
+    ExaRasterAdamSegment seg[ADAM_MAX_SEGMENTS];
+};
 
 namespace {
 
@@ -119,9 +131,52 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_step(AdamArgs A) {
 
 }  // namespace
 
-hipError_t launch_adam_step(const AdamArgs& A, hipStream_t s) {
-    hipLaunchKernelGGL(adam_step, dim3(A.start[A.n_seg]), dim3(ADAM_BLOCK), 0, s, A);
-    return hipGetLastError();
-}
-
 }  // namespace exa
+
+namespace exa_raster_impl {
+using namespace exa;
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" int exa_raster_adam_step(const ExaRasterAdamSegment* segs, int32_t n_seg, double beta1, double beta2, double eps,
+                                    void* stream) {
+    if (n_seg < 0) return fail(EXA_RASTER_E_INVALID, "adam: negative n_seg");
+    if (n_seg > 0 && !segs) return fail(EXA_RASTER_E_NULLPTR, "adam: segs is NULL");
+    if (!std::isfinite(beta1) || !std::isfinite(beta2) || !std::isfinite(eps))
+        return fail(EXA_RASTER_E_INVALID, "adam: beta1, beta2 and eps must be finite");
+    if (beta1 < 0.0 || beta1 >= 1.0 || beta2 < 0.0 || beta2 >= 1.0)
+        return fail(EXA_RASTER_E_INVALID, "adam: beta1 and beta2 must be in [0, 1)");
+    if (eps < 0.0) return fail(EXA_RASTER_E_INVALID, "adam: eps must be >= 0");
+    for (int32_t s = 0; s < n_seg; ++s) {      // every segment before the first launch
+        const ExaRasterAdamSegment& g = segs[s];
+        if (g.n < 0) return fail(EXA_RASTER_E_INVALID, "adam: negative n in a segment");
+        if (g.n > EXA_RASTER_ADAM_MAX_N) return fail(EXA_RASTER_E_INVALID, "adam: more than 2^36 elements in a segment (EXA_RASTER_ADAM_MAX_N)");
+        if (g.n == 0) continue;
+        if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq)
+            return fail(EXA_RASTER_E_NULLPTR, "adam: a segment with n > 0 holds a NULL pointer");
+        if (!std::isfinite(g.step_size) || !std::isfinite(g.bc2_sqrt))
+            return fail(EXA_RASTER_E_INVALID, "adam: step_size and bc2_sqrt must be finite");
+        if (!(g.bc2_sqrt > 0.0f)) return fail(EXA_RASTER_E_INVALID, "adam: bc2_sqrt must be > 0 (a step count >= 1)");
+    }
+    AdamArgs A;
+    A.w1 = (float)(1.0 - beta1); A.b2 = (float)beta2; A.w2 = (float)(1.0 - beta2); A.eps = (float)eps;
+    A.n_seg = 0;
+    A.start[0] = 0;
+    for (int32_t s = 0; s <= n_seg; ++s) {     // the non-empty segments, ADAM_MAX_SEGMENTS to a launch
+        if (s < n_seg && segs[s].n > 0) {
+            A.seg[A.n_seg] = segs[s];
+            A.start[A.n_seg + 1] = A.start[A.n_seg] + (uint32_t)((segs[s].n + EXA_RASTER_ADAM_CHUNK - 1) / EXA_RASTER_ADAM_CHUNK);
+            ++A.n_seg;
+        }
+        if (A.n_seg == ADAM_MAX_SEGMENTS || (s == n_seg && A.n_seg > 0)) {
+            for (int k = A.n_seg + 1; k <= ADAM_MAX_SEGMENTS; ++k) A.start[k] = A.start[A.n_seg];
+            for (int k = A.n_seg; k < ADAM_MAX_SEGMENTS; ++k) A.seg[k] = ExaRasterAdamSegment{};
+            hipLaunchKernelGGL(adam_step, dim3(A.start[A.n_seg]), dim3(ADAM_BLOCK), 0, static_cast<hipStream_t>(stream), A);
+            if (int rc = launched("adam_step")) return rc;
+            A.n_seg = 0;
+        }
+    }
+    return 0;
+}

@@ -586,92 +586,5 @@ inline bool split_sort(int subtiles) { return subtiles >= dev_knobs().split_subt
 // compose_kernel scans the sub-tile ranges in trips of this many cells, with a carry from trip to trip (compose.hip).
 constexpr int COMPOSE_TRIP_CELLS = 256;
 __host__ __device__ inline int compose_scan_trips(int cells) { return (cells + COMPOSE_TRIP_CELLS - 1) / COMPOSE_TRIP_CELLS; }
-hipError_t launch_ssim_fwd(int N, int H, int W, const float* img1, const float* img2, float* map, float* dm_dmu1,
-                           float* dm_dE11, float* dm_dE12, hipStream_t s);
-hipError_t launch_ssim_bwd(int N, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
-                           const float* dm_dmu1, const float* dm_dE11, const float* dm_dE12, float* dL_dimg1,
-                           hipStream_t s);
-hipError_t launch_photo_loss(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* l1w,
-                             const float* smask, float w_l1, float w_ssim, float* maps, float* partials, float* dL_dx,
-                             int stage, hipStream_t s);
-hipError_t launch_l1(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* mask,
-                     const float* bg, const float* g, float* out, int backward, hipStream_t s);
-hipError_t launch_densify_stats(int P, const float* g2d, const int32_t* radii, float* accum, float* cnt, float* rmax,
-                                hipStream_t s);
-// scene_assets.hip: the scene-Gaussian stage (sizes and the degree are the caller's to check)
-hipError_t launch_scene_assets_fwd(int P, int Mr, int deg, const float* mean, const float* opacity, const float* scale,
-                                   const float* rotation, const float* dc, const float* rest, const float* cam_R,
-                                   const float* cam_t, float* opacity_out, float* scale_out, float* rotation_out,
-                                   float* rgb, hipStream_t s);
-hipError_t launch_scene_assets_bwd(int P, int Mr, int deg, const float* mean, const float* rotation, const float* dc,
-                                   const float* rest, const float* cam_R, const float* cam_t, const float* opacity_out,
-                                   const float* scale_out, const float* g_opacity_out, const float* g_scale_out,
-                                   const float* g_rotation_out, const float* g_rgb, float* g_mean, float* g_opacity,
-                                   float* g_scale, float* g_rotation, float* g_dc, float* g_rest, hipStream_t s);
-// face_loss.hip: the face-composited L1 term and the composites (sizes, the window and the pointers are the caller's to
-// check).  face_l1_blocks: the workgroups (= partial sums) of the forward; face_image_blocks: those of a full-image walk.
-int64_t face_l1_blocks(int B, int cw, int ch);
-int64_t face_image_blocks(int B, int H, int W);
-hipError_t launch_face_l1_fwd(int B, int C, int H, int W, const int* crop, const float* img, const float* face,
-                              const float* tgt, float* map, float* partials, hipStream_t s);
-hipError_t launch_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out, hipStream_t s);
-// l1 != 0: the L1 term's backward (one of g_map / g_mean); l1 == 0: the hard composite's (g_map = dL_dout, crop = the image)
-hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, const float* img, const float* face,
-                           const float* tgt, const float* g_map, const float* g_mean, int64_t n_elements, float* d_img,
-                           float* d_face, hipStream_t s);
-hipError_t launch_composite_fwd(int mode, int B, int C, int H, int W, const float* a, const float* sel, const float* b,
-                                float* out, float thr, hipStream_t s);
-// lpips.hip: the LPIPS (VGG-16) trunk both ways and the head (sizes, the window and the pointers are the caller's to
-// check).  The workspace is carved by lpips.hip alone; offsets and sizes are in floats.
-uint64_t lpips_workspace_floats(int B, int h, int w);
-uint64_t lpips_tap_offset_floats(int B, int h, int w, int tap);
-void lpips_tap_shape(int h, int w, int tap, int* th, int* tw, int* tc);
-int64_t lpips_head_blocks(int64_t npix);
-hipError_t launch_lpips_trunk_fwd(int B, int H, int W, const int* crop, const float* img, const float* shift_scale,
-                                  const float* const* wpk, const float* const* bias, float* ws, hipStream_t s);
-hipError_t launch_lpips_trunk_bwd(int B, int H, int W, const int* crop, const float* shift_scale, const float* const* wpk_t,
-                                  const float* w1, const float* const* head_grads, float* ws, float* dimg, hipStream_t s);
-hipError_t launch_lpips_normalize(int64_t N, int C, const float* f, float* out, hipStream_t s);
-hipError_t launch_lpips_head_fwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w, float* dmap,
-                                 float* partials, hipStream_t s);
-hipError_t launch_lpips_head_reduce(int B, int n_taps, const float* const* partials, const int64_t* npix, float* out,
-                                    hipStream_t s);
-hipError_t launch_lpips_head_bwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w,
-                                 const float* gout, float* dfo, hipStream_t s);
-// adam.hip: the Adam step of up to ADAM_MAX_SEGMENTS non-empty tensors, the kernel's argument block as the caller fills it
-// (everything in it is the caller's to check)
-constexpr int ADAM_MAX_SEGMENTS = 64;
-struct AdamArgs {
-    int32_t n_seg;                             // 1 .. ADAM_MAX_SEGMENTS, every one with n > 0
-    float w1, b2, w2, eps;                     // (float)(1 - beta1), (float)beta2, (float)(1 - beta2), (float)eps
-    uint32_t start[ADAM_MAX_SEGMENTS + 1];     // first chunk of every segment; start[n_seg] = the grid
-    ExaRasterAdamSegment seg[ADAM_MAX_SEGMENTS];
-};
-hipError_t launch_adam_step(const AdamArgs& A, hipStream_t s);
-// densify.hip: the classification with its scan, and the move of up to DENSIFY_MAX_SEGMENTS tensors; the argument blocks as
-// the caller fills them (everything in them is the caller's to check)
-constexpr int DENSIFY_MAX_SEGMENTS = 64;
-struct DensifyPlanArgs {
-    int32_t P0;
-    int32_t prune_big;
-    const float *grad_accum, *track_cnt, *scale, *opacity;
-    const float* radius_max;                   // NULL: no screen-space rule
-    const float* extent;
-    const uint8_t* mask;                       // not NULL: mask mode, the six pointers above are not looked at
-    float grad_thr, dense_percent, opacity_min, child_div, screen_size_max;
-    uint8_t* codes;                            // the sections of the workspace
-    uint4* counts;
-};
-struct DensifyMoveArgs {
-    int32_t P0, split_factor, n_keep, n_clone, n_split, n_cand, n_seg;
-    float child_div;                           // (float)(0.8 * split_factor)
-    const uint4* record;                       // the sections of the workspace
-    const uint4* offsets;
-    const uint8_t* codes;
-    const float *rotation, *scale, *noise;     // the children's sources
-    ExaRasterDensifySegment seg[DENSIFY_MAX_SEGMENTS];
-};
-hipError_t launch_densify_plan(const DensifyPlanArgs& A, uint4* record, hipStream_t s);
-hipError_t launch_densify_move(const DensifyMoveArgs& A, hipStream_t s);
 
 }  // namespace exa

@@ -21,11 +21,40 @@
 // All accesses are 4 bytes wide: none of the reference's row widths (1, 3, 6, 45) lets a 16-byte access stay inside a row.
 // No global atomics, no memset, no allocation, no synchronisation: the same inputs give the same bits.
 #include <float.h>
-#include "common.h"
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/exa_raster.h"
+#include "abi_status.h"
 #include "rot6d.h"
 #include "wave_scan.h"
 
 namespace exa {
+
+// the kernels' argument blocks, as exa_raster_densify_plan / exa_raster_densify_move fill them: the classification with its
+// scan, and the move of up to DENSIFY_MAX_SEGMENTS tensors
+constexpr int DENSIFY_MAX_SEGMENTS = 64;
+struct DensifyPlanArgs {
+    int32_t P0;
+    int32_t prune_big;
+    const float *grad_accum, *track_cnt, *scale, *opacity;
+    const float* radius_max;                   // NULL: no screen-space rule
+    const float* extent;
+    const uint8_t* mask;                       // not NULL: mask mode, the six pointers above are not looked at
+    float grad_thr, dense_percent, opacity_min, child_div, screen_size_max;
+    uint8_t* codes;                            // the sections of the workspace
+    uint4* counts;
+};
+struct DensifyMoveArgs {
+    int32_t P0, split_factor, n_keep, n_clone, n_split, n_cand, n_seg;
+    float child_div;                           // (float)(0.8 * split_factor)
+    const uint4* record;                       // the sections of the workspace
+    const uint4* offsets;
+    const uint8_t* codes;
+    const float *rotation, *scale, *noise;     // the children's sources
+    ExaRasterDensifySegment seg[DENSIFY_MAX_SEGMENTS];
+};
 
 namespace {
 
@@ -230,19 +259,139 @@ __global__ __launch_bounds__(DB) void densify_move(DensifyMoveArgs A) {
 
 }  // namespace
 
-hipError_t launch_densify_plan(const DensifyPlanArgs& A, uint4* record, hipStream_t s) {
-    const int nb = (int)(((int64_t)A.P0 + DB - 1) / DB);
-    hipLaunchKernelGGL(densify_classify, dim3(nb), dim3(DB), 0, s, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(densify_scan, dim3(1), dim3(DS), 0, s, A.counts, nb, record);
-    return hipGetLastError();
-}
-
-hipError_t launch_densify_move(const DensifyMoveArgs& A, hipStream_t s) {
-    const int nb = (int)(((int64_t)A.P0 + DB - 1) / DB);
-    hipLaunchKernelGGL(densify_move, dim3(nb), dim3(DB), 0, s, A);
-    return hipGetLastError();
-}
-
 }  // namespace exa
+
+// ---- C entry points (include/exa_raster.h): checks, the argument blocks, the launches --------------------------------------
+namespace exa_raster_impl {
+
+using namespace exa;
+
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+
+// the workspace: the record of the four totals | 16 bytes per workgroup of rows | the codes, one byte per row
+static uint64_t densify_blocks(int32_t P0) { return ((uint64_t)P0 + DB - 1) / DB; }
+static uint64_t densify_bytes(int32_t P0) { return 16 + 16 * densify_blocks(P0) + 16 * (((uint64_t)P0 + 15) / 16); }
+
+static int densify_check_workspace(int32_t P0, const void* workspace, uint64_t workspace_bytes) {
+    if (!workspace) return fail(EXA_RASTER_E_NULLPTR, "densify: workspace is NULL");
+    if (workspace_bytes < densify_bytes(P0))
+        return fail(EXA_RASTER_E_WORKSPACE, "densify: workspace smaller than exa_raster_densify_workspace_size");
+    if ((uintptr_t)workspace & 15) return fail(EXA_RASTER_E_WORKSPACE, "densify: workspace must be 16-byte aligned");
+    return 0;
+}
+
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" {
+
+int exa_raster_densify_workspace_size(int32_t P0, uint64_t* bytes) {
+    if (!bytes) return fail(EXA_RASTER_E_NULLPTR, "densify: bytes is NULL");
+    if (P0 < 0) return fail(EXA_RASTER_E_INVALID, "densify: negative P0");
+    *bytes = densify_bytes(P0);
+    return 0;
+}
+
+int exa_raster_densify_plan(int32_t P0, const float* grad_accum, const float* track_cnt, const float* scale,
+                            const float* opacity, const float* radius_max, const float* extent, const uint8_t* mask,
+                            double grad_thr, double dense_percent, double opacity_min, int32_t prune_big,
+                            int32_t split_factor, double screen_size_max, void* workspace, uint64_t workspace_bytes,
+                            void* stream) {
+    if (P0 < 0) return fail(EXA_RASTER_E_INVALID, "densify: negative P0");
+    if (split_factor < 1 || split_factor > 8) return fail(EXA_RASTER_E_INVALID, "densify: split_factor must be in 1..8");
+    if (P0 == 0) return 0;
+    if (!mask && (!grad_accum || !track_cnt || !scale || !opacity || !extent))
+        return fail(EXA_RASTER_E_NULLPTR, "densify: NULL argument");
+    if (int rc = densify_check_workspace(P0, workspace, workspace_bytes)) return rc;
+    char* const ws = static_cast<char*>(workspace);
+    DensifyPlanArgs A;
+    A.P0 = P0;
+    A.prune_big = prune_big != 0;
+    A.grad_accum = grad_accum; A.track_cnt = track_cnt; A.scale = scale; A.opacity = opacity; A.extent = extent;
+    A.radius_max = (prune_big && screen_size_max > 0.0) ? radius_max : nullptr;
+    A.mask = mask;
+    A.grad_thr = (float)grad_thr; A.dense_percent = (float)dense_percent; A.opacity_min = (float)opacity_min;
+    A.child_div = (float)(0.8 * split_factor);
+    A.screen_size_max = (float)screen_size_max;
+    A.counts = reinterpret_cast<uint4*>(ws + 16);
+    A.codes = reinterpret_cast<uint8_t*>(ws + 16 + 16 * densify_blocks(P0));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nb = (int)densify_blocks(P0);
+    hipLaunchKernelGGL(densify_classify, dim3(nb), dim3(DB), 0, s, A);
+    if (int rc = launched("densify_plan")) return rc;
+    hipLaunchKernelGGL(densify_scan, dim3(1), dim3(DS), 0, s, A.counts, nb, reinterpret_cast<uint4*>(ws));
+    return launched("densify_plan");
+}
+
+int exa_raster_densify_move(int32_t P0, int32_t split_factor, const void* workspace, uint64_t workspace_bytes,
+                            int32_t n_keep, int32_t n_clone, int32_t n_split, int32_t n_cand,
+                            const ExaRasterDensifySegment* segs, int32_t n_seg, const float* rotation, const float* scale,
+                            const float* noise, void* stream) {
+    if (P0 < 0 || n_seg < 0) return fail(EXA_RASTER_E_INVALID, "densify: negative size");
+    if (split_factor < 1 || split_factor > 8) return fail(EXA_RASTER_E_INVALID, "densify: split_factor must be in 1..8");
+    if (n_keep < 0 || n_clone < 0 || n_split < 0 || n_cand < 0 || n_keep > P0 || n_clone > P0 || n_cand > P0 ||
+        n_split > n_cand)
+        return fail(EXA_RASTER_E_INVALID, "densify: the totals are not those of a plan over P0 rows");
+    if (P0 == 0 || n_seg == 0) return 0;
+    if (!segs) return fail(EXA_RASTER_E_NULLPTR, "densify: segs is NULL");
+    if (int rc = densify_check_workspace(P0, workspace, workspace_bytes)) return rc;
+    const int64_t n_out = (int64_t)n_keep + n_clone + (int64_t)split_factor * n_split;
+    bool any_mean = false;
+    for (int32_t s = 0; s < n_seg; ++s) {
+        const ExaRasterDensifySegment& g = segs[s];
+        if (g.row_floats < 1) return fail(EXA_RASTER_E_INVALID, "densify: row_floats must be >= 1");
+        if (g.role < EXA_RASTER_DENSIFY_COPY || g.role > EXA_RASTER_DENSIFY_SCALE)
+            return fail(EXA_RASTER_E_INVALID, "densify: unknown role");
+        if (g.role == EXA_RASTER_DENSIFY_MEAN && g.row_floats != 3)
+            return fail(EXA_RASTER_E_INVALID, "densify: a MEAN segment has row_floats = 3");
+        if (g.dst_rows < n_out) return fail(EXA_RASTER_E_INVALID, "densify: the totals do not fit dst (dst_rows < n_out)");
+        if (g.row_floats > (INT64_C(1) << 40) / ((int64_t)P0 + n_out + 1))
+            return fail(EXA_RASTER_E_INVALID, "densify: a segment of more than 2^40 floats");
+        if (!g.src || (n_out > 0 && !g.dst)) return fail(EXA_RASTER_E_NULLPTR, "densify: a segment holds a NULL pointer");
+        any_mean |= g.role == EXA_RASTER_DENSIFY_MEAN;
+    }
+    if (any_mean && (!rotation || !scale || (n_cand > 0 && !noise)))
+        return fail(EXA_RASTER_E_NULLPTR, "densify: a MEAN segment needs rotation, scale and noise");
+    // every written range against every range of the call: sorted by start, one sweep
+    struct Span { uintptr_t lo, hi; bool written; };
+    std::vector<Span> spans;
+    auto add = [&spans](const void* p, uint64_t bytes, bool written) {
+        if (p && bytes) spans.push_back({(uintptr_t)p, (uintptr_t)p + bytes, written});
+    };
+    add(workspace, densify_bytes(P0), false);
+    if (any_mean) {
+        add(rotation, (uint64_t)P0 * 24, false);
+        add(scale, (uint64_t)P0 * 12, false);
+        add(noise, (uint64_t)split_factor * n_cand * 12, false);
+    }
+    for (int32_t s = 0; s < n_seg; ++s) {
+        add(segs[s].src, (uint64_t)P0 * segs[s].row_floats * 4, false);
+        add(segs[s].dst, (uint64_t)n_out * segs[s].row_floats * 4, true);
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.lo < b.lo || (a.lo == b.lo && a.hi < b.hi); });
+    uintptr_t w_end = 0, r_end = 0;
+    for (const Span& sp : spans) {
+        if (sp.lo < w_end || (sp.written && sp.lo < r_end))
+            return fail(EXA_RASTER_E_ALIAS, "densify: a dst range overlaps another range of the call");
+        if (sp.written) w_end = std::max(w_end, sp.hi); else r_end = std::max(r_end, sp.hi);
+    }
+    const char* const ws = static_cast<const char*>(workspace);
+    DensifyMoveArgs A;
+    A.P0 = P0; A.split_factor = split_factor;
+    A.n_keep = n_keep; A.n_clone = n_clone; A.n_split = n_split; A.n_cand = n_cand;
+    A.child_div = (float)(0.8 * split_factor);
+    A.record = reinterpret_cast<const uint4*>(ws);
+    A.offsets = reinterpret_cast<const uint4*>(ws + 16);
+    A.codes = reinterpret_cast<const uint8_t*>(ws + 16 + 16 * densify_blocks(P0));
+    A.rotation = rotation; A.scale = scale; A.noise = noise;
+    for (int32_t s0 = 0; s0 < n_seg; s0 += DENSIFY_MAX_SEGMENTS) {
+        A.n_seg = std::min<int32_t>(DENSIFY_MAX_SEGMENTS, n_seg - s0);
+        for (int k = 0; k < DENSIFY_MAX_SEGMENTS; ++k) A.seg[k] = k < A.n_seg ? segs[s0 + k] : ExaRasterDensifySegment{};
+        hipLaunchKernelGGL(densify_move, dim3((int)densify_blocks(P0)), dim3(DB), 0, static_cast<hipStream_t>(stream), A);
+        if (int rc = launched("densify_move")) return rc;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 // by pixel.  Workgroups are BLOCK = 256 threads (4 waves) on a one-dimensional grid over (image, row, run).
 // No atomics; LDS only for the four wave sums of a workgroup sum.
 #include "common.h"
+#include "image_checks.h"
 
 namespace exa {
 
@@ -207,44 +208,42 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 }  // namespace
 
+}  // namespace exa
+
+// ---- C entry points (include/exa_raster.h): checks, then the launch --------------------------------------------------------
+namespace exa_raster_impl {
+
+using namespace exa;
+
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+
 // the runs of a window row: a window of cw > 0 pixels touches at most (cw + 6) / 4 runs of 4 pixels, wherever it starts
 static int window_runs(int cw) { return (cw + 6) / FACE_RUN; }
 
-int64_t face_l1_blocks(int B, int cw, int ch) {
+// the workgroups (= partial sums) of the L1 term's forward, and those of a full-image walk
+static int64_t face_l1_blocks(int B, int cw, int ch) {
     if (B <= 0 || cw <= 0 || ch <= 0) return 0;
     return ((int64_t)B * ch * window_runs(cw) + BLOCK - 1) / BLOCK;
 }
 
-int64_t face_image_blocks(int B, int H, int W) {
+static int64_t face_image_blocks(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
     return ((int64_t)B * H * ((W + FACE_RUN - 1) / FACE_RUN) + BLOCK - 1) / BLOCK;
 }
 
-hipError_t launch_face_l1_fwd(int B, int C, int H, int W, const int* crop, const float* img, const float* face,
-                              const float* tgt, float* map, float* partials, hipStream_t s) {
-    const int64_t blocks = face_l1_blocks(B, crop[2], crop[3]);
-    if (blocks == 0 || C == 0 || (!map && !partials)) return hipSuccess;
-    FaceL1Args a = {};
-    a.C = C; a.H = H; a.W = W; a.cx0 = crop[0]; a.cy0 = crop[1]; a.cw = crop[2]; a.ch = crop[3];
-    a.runs = window_runs(a.cw);
-    a.total = (unsigned)((int64_t)B * a.ch * a.runs);
-    a.vec = W % FACE_RUN == 0 && aligned16(img) && aligned16(face) && aligned16(tgt);
-    a.map_vec = a.cw % FACE_RUN == 0 && a.cx0 % FACE_RUN == 0 && aligned16(map);
-    a.img = img; a.face = face; a.tgt = tgt; a.map = map; a.partials = partials;
-    face_l1_fwd_kernel<<<(unsigned)blocks, BLOCK, 0, s>>>(a);
-    return hipGetLastError();
+// the one-dimensional grids index their runs of 4 pixels with 32 bits
+static int check_face_runs(int32_t B, int32_t H, int32_t W) {
+    if ((int64_t)B * H * ((W + 3) / 4 + 1) > 0x7fffffffLL)
+        return fail(EXA_RASTER_E_INVALID, "face loss: more than 2^31 - 1 runs of 4 pixels");
+    return 0;
 }
 
-hipError_t launch_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out, hipStream_t s) {
-    face_l1_reduce_kernel<<<1, BLOCK, 0, s>>>((long long)n_partials, (float)n_elements, partials, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, const float* img, const float* face,
+// l1 != 0: the L1 term's backward (one of g_map / g_mean); l1 == 0: the hard composite's (g_map = dL_dout, crop = the image)
+static int launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, const float* img, const float* face,
                            const float* tgt, const float* g_map, const float* g_mean, int64_t n_elements, float* d_img,
-                           float* d_face, hipStream_t s) {
+                           float* d_face, void* stream, const char* where) {
     const int64_t blocks = face_image_blocks(B, H, W);
-    if (blocks == 0 || (!d_img && !d_face)) return hipSuccess;
+    if (blocks == 0 || (!d_img && !d_face)) return 0;
     FaceL1Args a = {};
     a.C = C; a.H = H; a.W = W; a.cx0 = crop[0]; a.cy0 = crop[1]; a.cw = crop[2]; a.ch = crop[3];
     a.runs = (W + FACE_RUN - 1) / FACE_RUN;
@@ -254,24 +253,98 @@ hipError_t launch_face_bwd(int l1, int B, int C, int H, int W, const int* crop, 
     a.map_vec = a.cw % FACE_RUN == 0 && a.cx0 % FACE_RUN == 0 && aligned16(g_map);
     a.img = img; a.face = face; a.tgt = tgt; a.g_map = g_map; a.g_mean = g_mean; a.n = (float)n_elements;
     a.d_img = d_img; a.d_face = d_face;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (l1) face_bwd_kernel<true><<<(unsigned)blocks, BLOCK, 0, s>>>(a);
     else face_bwd_kernel<false><<<(unsigned)blocks, BLOCK, 0, s>>>(a);
-    return hipGetLastError();
+    return launched(where);
 }
 
-hipError_t launch_composite_fwd(int mode, int B, int C, int H, int W, const float* a, const float* sel, const float* b,
-                                float* out, float thr, hipStream_t s) {
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" {
+
+int64_t exa_face_l1_blocks(int32_t B, int32_t C, int32_t crop_w, int32_t crop_h) {
+    if (B < 0 || C <= 0 || crop_w < 0 || crop_h < 0) return 0;
+    return face_l1_blocks(B, crop_w, crop_h);
+}
+
+int exa_face_l1_forward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                        const float* face, const float* img_target, float* l1_map, float* partials, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((rc = check_face_runs(B, H, W))) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !face || !img_target))
+        return fail(EXA_RASTER_E_NULLPTR, "face_l1: NULL argument");
+    const int64_t blocks = face_l1_blocks(B, crop[2], crop[3]);
+    if (blocks == 0 || C == 0 || (!l1_map && !partials)) return 0;
+    FaceL1Args a = {};
+    a.C = C; a.H = H; a.W = W; a.cx0 = crop[0]; a.cy0 = crop[1]; a.cw = crop[2]; a.ch = crop[3];
+    a.runs = window_runs(a.cw);
+    a.total = (unsigned)((int64_t)B * a.ch * a.runs);
+    a.vec = W % FACE_RUN == 0 && aligned16(img_out) && aligned16(face) && aligned16(img_target);
+    a.map_vec = a.cw % FACE_RUN == 0 && a.cx0 % FACE_RUN == 0 && aligned16(l1_map);
+    a.img = img_out; a.face = face; a.tgt = img_target; a.map = l1_map; a.partials = partials;
+    face_l1_fwd_kernel<<<(unsigned)blocks, BLOCK, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return launched("face_l1_fwd");
+}
+
+int exa_face_l1_reduce(int64_t n_partials, int64_t n_elements, const float* partials, float* out_mean, void* stream) {
+    if (n_partials < 0 || n_elements < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (!out_mean || (n_partials > 0 && !partials)) return fail(EXA_RASTER_E_NULLPTR, "face_l1 reduce: NULL argument");
+    face_l1_reduce_kernel<<<1, BLOCK, 0, static_cast<hipStream_t>(stream)>>>((long long)n_partials, (float)n_elements, partials,
+                                                                             out_mean);
+    return launched("face_l1_reduce");
+}
+
+int exa_face_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                         const float* face, const float* img_target, const float* dL_dmap, const float* dL_dmean,
+                         int64_t n_elements, float* dL_dimg, float* dL_dface, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((rc = check_face_runs(B, H, W))) return rc;
+    if ((dL_dmap != nullptr) == (dL_dmean != nullptr))
+        return fail(EXA_RASTER_E_INVALID, "face_l1 backward: pass exactly one of dL_dmap / dL_dmean");
+    if (dL_dmean && n_elements < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if ((int64_t)B * crop[2] * crop[3] > 0 && (dL_dimg || dL_dface) && (!img_out || !face || !img_target))
+        return fail(EXA_RASTER_E_NULLPTR, "face_l1: NULL argument");
+    return launch_face_bwd(1, B, C, H, W, crop, img_out, face, img_target, dL_dmap, dL_dmean, n_elements, dL_dimg, dL_dface,
+                           stream, "face_l1_bwd");
+}
+
+int exa_composite_forward(int32_t mode, int32_t B, int32_t C, int32_t H, int32_t W, const float* a, const float* sel,
+                          const float* b, float* out, float thr, void* stream) {
+    if (mode != EXA_COMPOSITE_FACE_HARD && mode != EXA_COMPOSITE_FACE_SOFT && mode != EXA_COMPOSITE_FOREGROUND)
+        return fail(EXA_RASTER_E_INVALID, "composite: unknown mode");
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (int rc = check_face_runs(B, H, W)) return rc;
+    if ((int64_t)B * C * H * W > 0 && (!sel || !b || !out || (mode == EXA_COMPOSITE_FOREGROUND && !a)))
+        return fail(EXA_RASTER_E_NULLPTR, "composite: NULL argument");
     const int64_t blocks = face_image_blocks(B, H, W);
-    if (blocks == 0 || C == 0) return hipSuccess;
+    if (blocks == 0 || C == 0) return 0;
     CompositeArgs p = {};
     p.C = C; p.H = H; p.W = W; p.runs = (W + FACE_RUN - 1) / FACE_RUN;
     p.total = (unsigned)((int64_t)B * H * p.runs);
     p.vec = W % FACE_RUN == 0 && aligned16(a) && aligned16(sel) && aligned16(b) && aligned16(out);
     p.a = a; p.sel = sel; p.b = b; p.out = out; p.thr = thr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (mode == EXA_COMPOSITE_FACE_HARD) composite_fwd_kernel<EXA_COMPOSITE_FACE_HARD><<<(unsigned)blocks, BLOCK, 0, s>>>(p);
     else if (mode == EXA_COMPOSITE_FACE_SOFT) composite_fwd_kernel<EXA_COMPOSITE_FACE_SOFT><<<(unsigned)blocks, BLOCK, 0, s>>>(p);
     else composite_fwd_kernel<EXA_COMPOSITE_FOREGROUND><<<(unsigned)blocks, BLOCK, 0, s>>>(p);
-    return hipGetLastError();
+    return launched("composite_fwd");
 }
 
-}  // namespace exa
+int exa_composite_backward(int32_t B, int32_t C, int32_t H, int32_t W, const float* img, const float* face,
+                           const float* dL_dout, float* dL_dimg, float* dL_dface, void* stream) {
+    (void)img;                                             // the selection is decided by the face render alone
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (int rc = check_face_runs(B, H, W)) return rc;
+    if ((int64_t)B * H * W > 0 && (dL_dimg || dL_dface) && (!face || !dL_dout))
+        return fail(EXA_RASTER_E_NULLPTR, "composite: NULL argument");
+    const int32_t crop[4] = {0, 0, W, H};
+    return launch_face_bwd(0, B, C, H, W, crop, nullptr, face, nullptr, dL_dout, nullptr, 0, dL_dimg, dL_dface, stream,
+                           "composite_bwd");
+}
+
+}  // extern "C"

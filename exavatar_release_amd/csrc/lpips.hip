@@ -20,6 +20,7 @@
 //                     the crop come from this kernel.
 //   lpips_normalize / lpips_head_fwd / lpips_head_reduce / lpips_head_bwd   the head, one thread per tap pixel.
 #include "common.h"
+#include "image_checks.h"
 
 namespace exa {
 
@@ -412,50 +413,126 @@ __global__ __launch_bounds__(BLOCK) void lpips_head_bwd(int npix, int C, const f
 
 unsigned blocks_of(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
-#define LP_CHECK()                                   \
-    do {                                             \
-        const hipError_t e_ = hipGetLastError();     \
-        if (e_ != hipSuccess) return e_;             \
-    } while (0)
-
 }  // namespace
 
-uint64_t lpips_workspace_floats(int B, int h, int w) { return make_layout(B, h, w).floats; }
+}  // namespace exa
 
-uint64_t lpips_tap_offset_floats(int B, int h, int w, int tap) { return make_layout(B, h, w).act[TAP_LAYER[tap]]; }
+// ---- C entry points (include/exa_raster.h): checks, then the launches ------------------------------------------------------
+namespace exa_raster_impl {
 
-void lpips_tap_shape(int h, int w, int tap, int* th, int* tw, int* tc) {
-    *th = h >> tap; *tw = w >> tap; *tc = L_COUT[TAP_LAYER[tap]];
+using namespace exa;
+
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+
+#define LP_CHECK(where)                              \
+    do {                                             \
+        if (int rc_ = launched(where)) return rc_;   \
+    } while (0)
+
+static int64_t head_blocks(int64_t npix) { return (npix + BLOCK - 1) / BLOCK; }
+
+// B images, a crop of h x w: the sizes the LPIPS kernels index with 32 bits
+static int check_lpips_sizes(int32_t B, int32_t h, int32_t w) {
+    if (B < 0 || h < 0 || w < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (B > 0 && (h < EXA_LPIPS_MIN_CROP || w < EXA_LPIPS_MIN_CROP))
+        return fail(EXA_RASTER_E_INVALID, "lpips: the crop is smaller than 16 x 16 (the fifth tap would be empty)");
+    if (B > 65535 || (int64_t)B * h * w > 0x7fffffffLL / 16)
+        return fail(EXA_RASTER_E_INVALID, "lpips: more than 65535 images or 2^27 - 1 crop pixels");
+    return 0;
 }
 
-hipError_t launch_lpips_trunk_fwd(int B, int H, int W, const int* crop, const float* img, const float* shift_scale,
-                                  const float* const* wpk, const float* const* bias, float* ws, hipStream_t s) {
+static int check_lpips_trunk(int32_t B, int32_t H, int32_t W, const int32_t* crop, uint64_t ws_bytes) {
+    int rc = check_crop(B, 3, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * H * W > 0x7fffffffLL) return fail(EXA_RASTER_E_INVALID, "lpips: more than 2^31 - 1 image pixels");
+    if ((rc = check_lpips_sizes(B, crop[3], crop[2]))) return rc;
+    if (ws_bytes < make_layout(B, crop[3], crop[2]).floats * sizeof(float))
+        return fail(EXA_RASTER_E_INVALID, "lpips: the workspace is smaller than exa_lpips_workspace_size()");
+    return 0;
+}
+
+// the head's arrays: B images of npix pixels and C channels, indexed with 32 bits per image
+static int check_lpips_head(int32_t B, int64_t npix, int32_t C) {
+    if (B < 0 || npix < 0 || C < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (C % 4 != 0 || C == 0) return fail(EXA_RASTER_E_INVALID, "lpips head: C must be a positive multiple of 4");
+    if (B > 65535 || npix > 0x7fffffffLL - 256)
+        return fail(EXA_RASTER_E_INVALID, "lpips head: more than 65535 images or 2^31 - 257 pixels per image");
+    return 0;
+}
+
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" {
+
+int exa_lpips_workspace_size(int32_t B, int32_t h, int32_t w, uint64_t* bytes) {
+    if (!bytes) return fail(EXA_RASTER_E_NULLPTR, "lpips: bytes is NULL");
+    if (int rc = check_lpips_sizes(B, h, w)) return rc;
+    *bytes = make_layout(B, h, w).floats * sizeof(float);
+    return 0;
+}
+
+int exa_lpips_tap_layout(int32_t B, int32_t h, int32_t w, int32_t tap, uint64_t* byte_offset, int32_t* shape) {
+    if (!byte_offset || !shape) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    if (tap < 0 || tap >= EXA_LPIPS_TAPS) return fail(EXA_RASTER_E_INVALID, "lpips: tap must be 0 .. 4");
+    if (int rc = check_lpips_sizes(B, h, w)) return rc;
+    *byte_offset = make_layout(B, h, w).act[TAP_LAYER[tap]] * sizeof(float);
+    shape[0] = h >> tap; shape[1] = w >> tap; shape[2] = L_COUT[TAP_LAYER[tap]];
+    return 0;
+}
+
+int exa_lpips_trunk_forward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* img,
+                            const float* shift_scale, const float* const* weights, const float* const* biases, void* ws_,
+                            uint64_t ws_bytes, void* stream) {
+    if (int rc = check_lpips_trunk(B, H, W, crop, ws_bytes)) return rc;
+    if (B == 0) return 0;
+    if (!img || !shift_scale || !weights || !biases || !ws_) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    for (int l = 0; l < EXA_LPIPS_LAYERS; ++l)
+        if (!weights[l] || !biases[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL weight or bias");
+    for (int c = 3; c < 6; ++c)
+        if (!(shift_scale[c] != 0.0f)) return fail(EXA_RASTER_E_INVALID, "lpips: a scale of the input map is 0 or NaN");
+    float* const ws = static_cast<float*>(ws_);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int cw = crop[2], ch = crop[3];
     const Layout L = make_layout(B, ch, cw);
     lpips_prep<<<blocks_of((uint64_t)B * ch * cw), BLOCK, 0, s>>>(B, H, W, crop[0], crop[1], cw, ch, shift_scale[0],
                                                                   shift_scale[1], shift_scale[2], shift_scale[3],
                                                                   shift_scale[4], shift_scale[5], img, ws + L.x);
-    LP_CHECK();
-    lpips_conv1<<<blocks_of((uint64_t)B * ch * cw * 16), BLOCK, 0, s>>>(B, ch, cw, ws + L.x, wpk[0], bias[0], ws + L.act[0]);
-    LP_CHECK();
+    LP_CHECK("lpips_trunk_fwd");
+    lpips_conv1<<<blocks_of((uint64_t)B * ch * cw * 16), BLOCK, 0, s>>>(B, ch, cw, ws + L.x, weights[0], biases[0],
+                                                                        ws + L.act[0]);
+    LP_CHECK("lpips_trunk_fwd");
     for (int l = 1; l < 13; ++l) {
         const int blk = L_BLOCK[l], src = L_BLOCK[l - 1];
         ConvArgs a = {};
         a.in = ws + L.act[l - 1]; a.Hs = L.h[src]; a.Ws = L.w[src]; a.pool = L_POOL[l];
         a.h = L.h[blk]; a.w = L.w[blk]; a.Cin = L_CIN[l]; a.Cout = L_COUT[l];
-        a.wpk = wpk[l]; a.bias = bias[l]; a.out = ws + L.act[l];
+        a.wpk = weights[l]; a.bias = biases[l]; a.out = ws + L.act[l];
         a.tiles_x = (a.w + CONV_TILE - 1) / CONV_TILE;
         const dim3 grid(a.tiles_x * ((a.h + CONV_TILE - 1) / CONV_TILE), a.Cout / 64, B);
         lpips_conv<FWD><<<grid, BLOCK, 0, s>>>(a);
-        LP_CHECK();
+        LP_CHECK("lpips_trunk_fwd");
     }
-    return hipSuccess;
+    return 0;
 }
 
-// head_grads[t]: dL/d(tap t) [B, h_t, w_t, C_t] without the ReLU mask; wpk_t[l]: the transposed, rotated weights of layer l
-// (l = 1 .. 12) in the convolution's image; w1: the first layer's [tap][ci][co]
-hipError_t launch_lpips_trunk_bwd(int B, int H, int W, const int* crop, const float* shift_scale, const float* const* wpk_t,
-                                  const float* w1, const float* const* head_grads, float* ws, float* dimg, hipStream_t s) {
+// head_grads[t]: dL/d(tap t) [B, h_t, w_t, C_t] without the ReLU mask; weights_t[l]: the transposed, rotated weights of
+// layer l (l = 1 .. 12) in the convolution's image; weights_t[0]: the first layer's [tap][ci][co]
+int exa_lpips_trunk_backward(int32_t B, int32_t H, int32_t W, const int32_t* crop, const float* shift_scale,
+                             const float* const* weights_t, const float* const* head_grads, void* ws_, uint64_t ws_bytes,
+                             float* dL_dimg, void* stream) {
+    if (int rc = check_lpips_trunk(B, H, W, crop, ws_bytes)) return rc;
+    if (B == 0) return 0;
+    if (!shift_scale || !weights_t || !head_grads || !ws_ || !dL_dimg) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL argument");
+    for (int l = 0; l < EXA_LPIPS_LAYERS; ++l)
+        if (!weights_t[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL weight or bias");
+    for (int t = 0; t < EXA_LPIPS_TAPS; ++t)
+        if (!head_grads[t]) return fail(EXA_RASTER_E_NULLPTR, "lpips: NULL head gradient");
+    for (int c = 3; c < 6; ++c)
+        if (!(shift_scale[c] != 0.0f)) return fail(EXA_RASTER_E_INVALID, "lpips: a scale of the input map is 0 or NaN");
+    float* const ws = static_cast<float*>(ws_);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     const int cw = crop[2], ch = crop[3];
     const Layout L = make_layout(B, ch, cw);
     float* g[2] = {ws + L.g0, ws + L.g1};
@@ -463,14 +540,14 @@ hipError_t launch_lpips_trunk_bwd(int B, int H, int W, const int* crop, const fl
     {
         const uint64_t n = (uint64_t)B * L.h[4] * L.w[4] * 512;
         lpips_relu_mask<<<blocks_of(n / 4), BLOCK, 0, s>>>((size_t)(n / 4), ws + L.act[12], head_grads[4], g[cur]);
-        LP_CHECK();
+        LP_CHECK("lpips_trunk_bwd");
     }
     for (int l = 12; l >= 1; --l) {      // dZ_l -> dZ_{l-1}
         const int blk = L_BLOCK[l], prev = L_BLOCK[l - 1];
         ConvArgs a = {};
         a.in = g[cur]; a.Hs = L.h[blk]; a.Ws = L.w[blk]; a.pool = 0;
         a.h = L.h[blk]; a.w = L.w[blk]; a.Cin = L_COUT[l]; a.Cout = L_CIN[l];
-        a.wpk = wpk_t[l]; a.out = g[cur ^ 1]; a.act = ws + L.act[l - 1];
+        a.wpk = weights_t[l]; a.out = g[cur ^ 1]; a.act = ws + L.act[l - 1];
         a.tiles_x = (a.w + CONV_TILE - 1) / CONV_TILE;
         const dim3 grid(a.tiles_x * ((a.h + CONV_TILE - 1) / CONV_TILE), a.Cout / 64, B);
         if (L_POOL[l]) {
@@ -479,46 +556,66 @@ hipError_t launch_lpips_trunk_bwd(int B, int H, int W, const int* crop, const fl
         } else {
             lpips_conv<BWD_PLAIN><<<grid, BLOCK, 0, s>>>(a);
         }
-        LP_CHECK();
+        LP_CHECK("lpips_trunk_bwd");
         cur ^= 1;
     }
     lpips_conv1_bwd<<<blocks_of((uint64_t)B * H * W), BLOCK, 0, s>>>(B, H, W, crop[0], crop[1], cw, ch, shift_scale[3],
-                                                                    shift_scale[4], shift_scale[5], g[cur], w1, dimg);
-    return hipGetLastError();
+                                                                    shift_scale[4], shift_scale[5], g[cur], weights_t[0],
+                                                                    dL_dimg);
+    return launched("lpips_trunk_bwd");
 }
 
-hipError_t launch_lpips_normalize(int64_t N, int C, const float* f, float* out, hipStream_t s) {
-    if (N == 0) return hipSuccess;
-    lpips_normalize<<<blocks_of((uint64_t)N), BLOCK, 0, s>>>((size_t)N, C, f, out);
-    return hipGetLastError();
+int exa_lpips_normalize(int64_t N, int32_t C, const float* f, float* out, void* stream) {
+    if (N < 0 || C < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (C % 4 != 0 || C == 0) return fail(EXA_RASTER_E_INVALID, "lpips head: C must be a positive multiple of 4");
+    if (N > 0x7fffffffLL * 256) return fail(EXA_RASTER_E_INVALID, "lpips head: more than 2^39 pixels");
+    if (N > 0 && (!f || !out)) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    if (N == 0) return 0;
+    lpips_normalize<<<blocks_of((uint64_t)N), BLOCK, 0, static_cast<hipStream_t>(stream)>>>((size_t)N, C, f, out);
+    return launched("lpips_normalize");
 }
 
-int64_t lpips_head_blocks(int64_t npix) { return (npix + BLOCK - 1) / BLOCK; }
+int64_t exa_lpips_head_blocks(int64_t npix) { return npix <= 0 ? 0 : head_blocks(npix); }
 
-hipError_t launch_lpips_head_fwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w, float* dmap,
-                                 float* partials, hipStream_t s) {
-    if (B == 0 || npix == 0) return hipSuccess;
-    lpips_head_fwd<<<dim3((unsigned)lpips_head_blocks(npix), B), BLOCK, 0, s>>>((int)npix, C, fo, nt, w, dmap, partials);
-    return hipGetLastError();
+int exa_lpips_head_forward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                           float* d_map, float* partials, void* stream) {
+    if (int rc = check_lpips_head(B, npix, C)) return rc;
+    if ((int64_t)B * npix > 0 && (!f_out || !n_target || !lin || !partials))
+        return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    if (B == 0 || npix == 0) return 0;
+    lpips_head_fwd<<<dim3((unsigned)head_blocks(npix), B), BLOCK, 0, static_cast<hipStream_t>(stream)>>>(
+        (int)npix, C, f_out, n_target, lin, d_map, partials);
+    return launched("lpips_head_fwd");
 }
 
-hipError_t launch_lpips_head_reduce(int B, int n_taps, const float* const* partials, const int64_t* npix, float* out,
-                                    hipStream_t s) {
-    if (B == 0) return hipSuccess;
+int exa_lpips_head_reduce(int32_t B, int32_t n_taps, const float* const* partials, const int64_t* npix, float* out,
+                          void* stream) {
+    if (B < 0 || B > 65535) return fail(EXA_RASTER_E_INVALID, "lpips head: B must be 0 .. 65535");
+    if (n_taps < 1 || n_taps > EXA_LPIPS_MAX_TAPS) return fail(EXA_RASTER_E_INVALID, "lpips head: n_taps must be 1 .. 8");
+    if (!partials || !npix || (B > 0 && !out)) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    for (int l = 0; l < n_taps; ++l) {
+        if (npix[l] <= 0 || npix[l] > 0x7fffffffLL - 256) return fail(EXA_RASTER_E_INVALID, "lpips head: a tap without pixels");
+        if (B > 0 && !partials[l]) return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    }
+    if (B == 0) return 0;
     ReduceArgs a = {};
     a.n_taps = n_taps; a.out = out;
     for (int l = 0; l < n_taps; ++l) {
-        a.partials[l] = partials[l]; a.nblk[l] = (int)lpips_head_blocks(npix[l]); a.npix[l] = (float)npix[l];
+        a.partials[l] = partials[l]; a.nblk[l] = (int)head_blocks(npix[l]); a.npix[l] = (float)npix[l];
     }
-    lpips_head_reduce<<<B, BLOCK, 0, s>>>(a);
-    return hipGetLastError();
+    lpips_head_reduce<<<B, BLOCK, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return launched("lpips_head_reduce");
 }
 
-hipError_t launch_lpips_head_bwd(int B, int64_t npix, int C, const float* fo, const float* nt, const float* w,
-                                 const float* gout, float* dfo, hipStream_t s) {
-    if (B == 0 || npix == 0) return hipSuccess;
-    lpips_head_bwd<<<dim3((unsigned)lpips_head_blocks(npix), B), BLOCK, 0, s>>>((int)npix, C, fo, nt, w, gout, dfo);
-    return hipGetLastError();
+int exa_lpips_head_backward(int32_t B, int64_t npix, int32_t C, const float* f_out, const float* n_target, const float* lin,
+                            const float* dL_dout, float* dL_df, void* stream) {
+    if (int rc = check_lpips_head(B, npix, C)) return rc;
+    if ((int64_t)B * npix > 0 && (!f_out || !n_target || !lin || !dL_dout || !dL_df))
+        return fail(EXA_RASTER_E_NULLPTR, "lpips head: NULL argument");
+    if (B == 0 || npix == 0) return 0;
+    lpips_head_bwd<<<dim3((unsigned)head_blocks(npix), B), BLOCK, 0, static_cast<hipStream_t>(stream)>>>(
+        (int)npix, C, f_out, n_target, lin, dL_dout, dL_df);
+    return launched("lpips_head_bwd");
 }
 
-}  // namespace exa
+}  // extern "C"

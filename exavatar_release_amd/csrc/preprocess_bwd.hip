@@ -749,12 +749,6 @@ __global__ __launch_bounds__(BLOCK) void densify_stats_kernel(int P, const float
     if (cnt) cnt[i] += 1.0f;
     if (rmax) rmax[i] = fmaxf(rmax[i], (float)r);
 }
-hipError_t launch_densify_stats(int P, const float* g2d, const int32_t* radii, float* accum, float* cnt, float* rmax,
-                                hipStream_t s) {
-    if (P == 0) return hipSuccess;
-    densify_stats_kernel<<<(P + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(P, g2d, radii, accum, cnt, rmax);
-    return hipGetLastError();
-}
 
 // Second pass of a summed batch of more than four views (preprocess_bwd_kernel<SUM, VW = 4>): the sums of the further
 // workgroup rows (views 4 ..), left in their scratch in the layout of the outputs, are added to the outputs of row 0 in row
@@ -808,3 +802,20 @@ hipError_t launch_preprocess_bwd(const PreprocessBwdArgs* a, int K, int sum_shar
 }
 
 }  // namespace exa
+
+namespace exa_raster_impl {
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+}  // namespace exa_raster_impl
+
+extern "C" int exa_raster_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t* radii, float* xyz_grad_accum,
+                                        float* track_cnt, float* radius_max, void* stream) {
+    using namespace exa;
+    using namespace exa_raster_impl;
+    if (P < 0) return fail(EXA_RASTER_E_INVALID, "P < 0");
+    if (P > 0 && !radii) return fail(EXA_RASTER_E_NULLPTR, "radii is NULL");
+    if (P > 0 && xyz_grad_accum && !dL_dmeans2D) return fail(EXA_RASTER_E_NULLPTR, "dL_dmeans2D is NULL");
+    if (P == 0) return 0;
+    densify_stats_kernel<<<(P + BLOCK - 1) / BLOCK, BLOCK, 0, static_cast<hipStream_t>(stream)>>>(
+        P, dL_dmeans2D, radii, xyz_grad_accum, track_cnt, radius_max);
+    return launched("densify_stats");
+}

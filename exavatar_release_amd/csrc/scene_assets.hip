@@ -11,7 +11,8 @@
 // HBM traffic per Gaussian at degree 3 (Mr = 15): forward reads 12 + 4 + 12 + 24 + 12 + 180 = 244 B and writes
 // 4 + 12 + 16 + 12 = 44 B; backward reads the 228 B of (mean, rotation, dc, rest), 16 B of saved outputs and 44 B of
 // cotangents and writes 12 + 4 + 12 + 24 + 12 + 180 = 244 B.
-#include "common.h"
+#include "../../include/exa_raster.h"
+#include "abi_status.h"
 #include "rot6d.h"
 
 namespace exa {
@@ -286,8 +287,18 @@ __global__ __launch_bounds__(SB) void scene_bwd(BwdArgs a) {
 
 }  // namespace scene
 
-#define EXA_SCENE_DISPATCH(KERNEL, ARGS)                                                                               \
-    switch (Mr * 4 + deg) {                                                                                            \
+}  // namespace exa
+
+// ---- C entry points (include/exa_raster.h): checks, then the launch --------------------------------------------------------
+namespace exa_raster_impl {
+
+using namespace exa;
+
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+
+// (check_scene has let through Mr in {0, 3, 8, 15}, 0 <= deg <= 3 and (deg + 1)^2 <= 1 + Mr: the default is never taken)
+#define EXA_SCENE_DISPATCH(KERNEL, ARGS, WHERE)                                                                        \
+    switch (Mr * 4 + sh_degree) {                                                                                      \
         case 0 * 4 + 0: scene::KERNEL<0, 0><<<grid, scene::SB, 0, s>>>(ARGS); break;                                   \
         case 3 * 4 + 0: scene::KERNEL<3, 0><<<grid, scene::SB, 0, s>>>(ARGS); break;                                   \
         case 3 * 4 + 1: scene::KERNEL<3, 1><<<grid, scene::SB, 0, s>>>(ARGS); break;                                   \
@@ -298,32 +309,70 @@ __global__ __launch_bounds__(SB) void scene_bwd(BwdArgs a) {
         case 15 * 4 + 1: scene::KERNEL<15, 1><<<grid, scene::SB, 0, s>>>(ARGS); break;                                 \
         case 15 * 4 + 2: scene::KERNEL<15, 2><<<grid, scene::SB, 0, s>>>(ARGS); break;                                 \
         case 15 * 4 + 3: scene::KERNEL<15, 3><<<grid, scene::SB, 0, s>>>(ARGS); break;                                 \
-        default: return hipErrorInvalidValue;                                                                          \
+        default: return fail_hip(hipErrorInvalidValue, WHERE);                                                         \
     }
 
-// The caller (api.hip) has checked P > 0, Mr in {0, 3, 8, 15}, 0 <= deg <= 3 and (deg + 1)^2 <= 1 + Mr.
-hipError_t launch_scene_assets_fwd(int P, int Mr, int deg, const float* mean, const float* opacity, const float* scale,
-                                   const float* rotation, const float* dc, const float* rest, const float* cam_R,
-                                   const float* cam_t, float* opacity_out, float* scale_out, float* rotation_out,
-                                   float* rgb, hipStream_t s) {
-    const scene::FwdArgs a = {P, mean, opacity, scale, rotation, dc, rest, cam_R, cam_t,
+static int check_scene(int32_t P, int32_t Mr, int32_t sh_degree) {
+    if (P < 0) return fail(EXA_RASTER_E_INVALID, "scene_assets: P < 0");
+    if (Mr != 0 && Mr != 3 && Mr != 8 && Mr != 15)
+        return fail(EXA_RASTER_E_INVALID, "scene_assets: Mr (rows of feature_rest) must be 0, 3, 8 or 15");
+    if (sh_degree < 0 || sh_degree > 3) return fail(EXA_RASTER_E_INVALID, "scene_assets: sh_degree must be 0 .. 3");
+    if ((sh_degree + 1) * (sh_degree + 1) > 1 + Mr)
+        return fail(EXA_RASTER_E_INVALID, "scene_assets: sh_degree needs (sh_degree + 1)^2 <= 1 + Mr coefficients");
+    return 0;
+}
+
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" {
+
+int exa_raster_scene_assets_forward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* opacity,
+                                    const float* scale, const float* rotation, const float* feature_dc,
+                                    const float* feature_rest, const float* cam_R, const float* cam_t,
+                                    float* opacity_out, float* scale_out, float* rotation_out, float* rgb,
+                                    void* stream) {
+    if (int rc = check_scene(P, Mr, sh_degree)) return rc;
+    if (P == 0) return 0;
+    if (!mean || !opacity || !scale || !rotation || !feature_dc || (Mr > 0 && !feature_rest))
+        return fail(EXA_RASTER_E_NULLPTR, "scene_assets: a parameter array is NULL");
+    if (!cam_R || !cam_t) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: cam_R / cam_t is NULL");
+    if (!opacity_out || !scale_out || !rotation_out || !rgb)
+        return fail(EXA_RASTER_E_NULLPTR, "scene_assets: an output array is NULL");
+    const scene::FwdArgs a = {P, mean, opacity, scale, rotation, feature_dc, feature_rest, cam_R, cam_t,
                               opacity_out, scale_out, rotation_out, rgb};
     const unsigned grid = ceil_div(P, scene::SB);
-    EXA_SCENE_DISPATCH(scene_fwd, a)
-    return hipGetLastError();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EXA_SCENE_DISPATCH(scene_fwd, a, "scene_fwd")
+    return launched("scene_fwd");
 }
 
-hipError_t launch_scene_assets_bwd(int P, int Mr, int deg, const float* mean, const float* rotation, const float* dc,
-                                   const float* rest, const float* cam_R, const float* cam_t, const float* opacity_out,
-                                   const float* scale_out, const float* g_opacity_out, const float* g_scale_out,
-                                   const float* g_rotation_out, const float* g_rgb, float* g_mean, float* g_opacity,
-                                   float* g_scale, float* g_rotation, float* g_dc, float* g_rest, hipStream_t s) {
-    const scene::BwdArgs a = {P, mean, rotation, dc, rest, cam_R, cam_t, opacity_out, scale_out,
-                              g_opacity_out, g_scale_out, g_rotation_out, g_rgb,
-                              g_mean, g_opacity, g_scale, g_rotation, g_dc, g_rest};
+int exa_raster_scene_assets_backward(int32_t P, int32_t Mr, int32_t sh_degree, const float* mean, const float* rotation,
+                                     const float* feature_dc, const float* feature_rest, const float* cam_R,
+                                     const float* cam_t, const float* opacity_out, const float* scale_out,
+                                     const float* grad_opacity_out, const float* grad_scale_out,
+                                     const float* grad_rotation_out, const float* grad_rgb, float* grad_mean,
+                                     float* grad_opacity, float* grad_scale, float* grad_rotation,
+                                     float* grad_feature_dc, float* grad_feature_rest, void* stream) {
+    if (int rc = check_scene(P, Mr, sh_degree)) return rc;
+    if (Mr == 0) grad_feature_rest = nullptr;
+    if (P == 0 || (!grad_mean && !grad_opacity && !grad_scale && !grad_rotation && !grad_feature_dc && !grad_feature_rest))
+        return 0;
+    if (grad_opacity && !opacity_out) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_opacity needs opacity_out");
+    if (grad_scale && !scale_out) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_scale needs scale_out");
+    if (grad_rotation && !rotation) return fail(EXA_RASTER_E_NULLPTR, "scene_assets: grad_rotation needs rotation");
+    if ((grad_mean || grad_feature_dc || grad_feature_rest) &&
+        (!mean || !feature_dc || (Mr > 0 && !feature_rest) || !cam_R || !cam_t))
+        return fail(EXA_RASTER_E_NULLPTR,
+                    "scene_assets: the colour gradients need mean, feature_dc, feature_rest, cam_R and cam_t");
+    const scene::BwdArgs a = {P, mean, rotation, feature_dc, feature_rest, cam_R, cam_t, opacity_out, scale_out,
+                              grad_opacity_out, grad_scale_out, grad_rotation_out, grad_rgb,
+                              grad_mean, grad_opacity, grad_scale, grad_rotation, grad_feature_dc, grad_feature_rest};
     const unsigned grid = ceil_div(P, scene::SB);
-    EXA_SCENE_DISPATCH(scene_bwd, a)
-    return hipGetLastError();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EXA_SCENE_DISPATCH(scene_bwd, a, "scene_bwd")
+    return launched("scene_bwd");
 }
 
-}  // namespace exa
+}  // extern "C"

@@ -18,6 +18,7 @@
 // conv2d's zero padding) is staged in LDS, filtered horizontally into LDS, then vertically from LDS.  Pure
 // streaming: reads 8 B/pixel, writes 4 (+12 with the derivative maps) B/pixel; backward reads 24, writes 4.
 #include "common.h"
+#include "image_checks.h"
 
 namespace exa {
 
@@ -408,50 +409,132 @@ __global__ __launch_bounds__(BLOCK) void l1_kernel(L1Args a, size_t total) {
     else a.out[i] = fabsf(d);
 }
 
-hipError_t launch_ssim_fwd(int N, int H, int W, const float* img1, const float* img2, float* map, float* dm_dmu1,
-                           float* dm_dE11, float* dm_dE12, hipStream_t s) {
-    if (N == 0 || H == 0 || W == 0) return hipSuccess;
-    const dim3 grid((W + ST - 1) / ST, (H + ST - 1) / ST, N), block(ST, ST, 1);
-    ssim_fwd_kernel<<<grid, block, 0, s>>>(H, W, img1, img2, map, dm_dmu1, dm_dE11, dm_dE12, make_window());
-    return hipGetLastError();
+}  // namespace exa
+
+// ---- C entry points (include/exa_raster.h): checks, then the launch --------------------------------------------------------
+namespace exa_raster_impl {
+
+using namespace exa;
+
+EXA_ABI_STATUS_SHARED("exa_raster")       // exa_raster_last_error() and its buffer are api.hip's
+
+// (declared in image_checks.h: the photometric and L1 terms here, the face loss and the LPIPS trunk use it)
+int check_crop(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if (!crop) return fail(EXA_RASTER_E_NULLPTR, "crop is NULL");
+    if (crop[0] < 0 || crop[1] < 0 || crop[2] < 0 || crop[3] < 0 || crop[0] + crop[2] > W || crop[1] + crop[3] > H)
+        return fail(EXA_RASTER_E_INVALID, "crop window outside the image");
+    return 0;
 }
 
-hipError_t launch_ssim_bwd(int N, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
-                           const float* dm_dmu1, const float* dm_dE11, const float* dm_dE12, float* dL_dimg1,
-                           hipStream_t s) {
-    if (N == 0 || H == 0 || W == 0) return hipSuccess;
-    const dim3 grid((W + ST - 1) / ST, (H + ST - 1) / ST, N), block(ST, ST, 1);
-    ssim_bwd_kernel<<<grid, block, 0, s>>>(H, W, img1, img2, dL_dmap, dm_dmu1, dm_dE11, dm_dE12, dL_dimg1, make_window());
-    return hipGetLastError();
-}
-
-hipError_t launch_photo_loss(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* l1w,
+// stage 0: the statistics (maps, partials); stage 1: the gradient from the stored maps
+static int launch_photo_loss(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* l1w,
                              const float* smask, float w_l1, float w_ssim, float* maps, float* partials, float* dL_dx,
-                             int stage, hipStream_t s) {
+                             int stage, void* stream, const char* where) {
     PhotoArgs a;
     a.C = C; a.H = H; a.W = W; a.cx0 = crop[0]; a.cy0 = crop[1]; a.cw = crop[2]; a.ch = crop[3];
-    if (B * C == 0 || a.cw <= 0 || a.ch <= 0) return hipSuccess;
+    if (B * C == 0 || a.cw <= 0 || a.ch <= 0) return 0;
     a.x = x; a.y = y; a.l1w = l1w; a.smask = smask; a.maps = maps; a.partials = partials; a.dL_dx = dL_dx;
     const float inv_n = 1.0f / ((float)B * (float)C * (float)a.cw * (float)a.ch);
     a.k_l1 = w_l1 * inv_n; a.k_ssim = w_ssim * inv_n;
     const dim3 grid((a.cw + PT - 1) / PT, (a.ch + PT - 1) / PT, B * C);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (stage == 0) photo_stats_kernel<<<grid, PBLOCK2, 0, s>>>(a, make_window());
     else photo_grad_kernel<<<grid, PBLOCK2, 0, s>>>(a, make_window());
-    return hipGetLastError();
+    return launched(where);
 }
 
-hipError_t launch_l1(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* mask,
-                     const float* bg, const float* g, float* out, int backward, hipStream_t s) {
+static int launch_l1(int B, int C, int H, int W, const int* crop, const float* x, const float* y, const float* mask,
+                     const float* bg, const float* g, float* out, int backward, void* stream, const char* where) {
     L1Args a;
     a.C = C; a.H = H; a.W = W; a.cx0 = crop[0]; a.cy0 = crop[1]; a.cw = crop[2]; a.ch = crop[3];
     a.x = x; a.y = y; a.mask = mask; a.bg = bg; a.g = g; a.out = out;
-    if (a.cw <= 0 || a.ch <= 0) return hipSuccess;
+    if (a.cw <= 0 || a.ch <= 0) return 0;
     const size_t total = (size_t)B * C * a.cw * a.ch;
-    if (total == 0) return hipSuccess;
+    if (total == 0) return 0;
     const unsigned blocks = (unsigned)((total + BLOCK - 1) / BLOCK);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (backward) l1_kernel<true><<<blocks, BLOCK, 0, s>>>(a, total);
     else l1_kernel<false><<<blocks, BLOCK, 0, s>>>(a, total);
-    return hipGetLastError();
+    return launched(where);
 }
 
-}  // namespace exa
+}  // namespace exa_raster_impl
+
+using namespace exa_raster_impl;
+
+extern "C" {
+
+int exa_ssim_forward(int32_t N, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_map,
+                     float* dm_dmu1, float* dm_dE11, float* dm_dE12, void* stream) {
+    if (N < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if ((int64_t)N * H * W > 0 && (!img1 || !img2 || !ssim_map)) return fail(EXA_RASTER_E_NULLPTR, "img / map is NULL");
+    if ((dm_dmu1 != nullptr) != (dm_dE11 != nullptr) || (dm_dmu1 != nullptr) != (dm_dE12 != nullptr))
+        return fail(EXA_RASTER_E_INVALID, "pass all three derivative maps or none");
+    if (N == 0 || H == 0 || W == 0) return 0;
+    const dim3 grid((W + ST - 1) / ST, (H + ST - 1) / ST, N), block(ST, ST, 1);
+    ssim_fwd_kernel<<<grid, block, 0, static_cast<hipStream_t>(stream)>>>(H, W, img1, img2, ssim_map, dm_dmu1, dm_dE11, dm_dE12,
+                                                                          make_window());
+    return launched("ssim_fwd");
+}
+
+int exa_ssim_backward(int32_t N, int32_t H, int32_t W, const float* img1, const float* img2, const float* dL_dmap,
+                      const float* dm_dmu1, const float* dm_dE11, const float* dm_dE12, float* dL_dimg1,
+                      void* stream) {
+    if (N < 0 || H < 0 || W < 0) return fail(EXA_RASTER_E_INVALID, "negative size");
+    if ((int64_t)N * H * W > 0 && (!img1 || !img2 || !dL_dmap || !dm_dmu1 || !dm_dE11 || !dm_dE12 || !dL_dimg1))
+        return fail(EXA_RASTER_E_NULLPTR, "ssim backward: NULL argument");
+    if (N == 0 || H == 0 || W == 0) return 0;
+    const dim3 grid((W + ST - 1) / ST, (H + ST - 1) / ST, N), block(ST, ST, 1);
+    ssim_bwd_kernel<<<grid, block, 0, static_cast<hipStream_t>(stream)>>>(H, W, img1, img2, dL_dmap, dm_dmu1, dm_dE11, dm_dE12,
+                                                                          dL_dimg1, make_window());
+    return launched("ssim_bwd");
+}
+
+int64_t exa_photo_loss_blocks(int32_t B, int32_t C, int32_t crop_w, int32_t crop_h) {
+    if (B < 0 || C < 0 || crop_w < 0 || crop_h < 0) return 0;
+    return (int64_t)B * C * ((crop_w + 31) / 32) * ((crop_h + 31) / 32);
+}
+
+int exa_photo_loss_forward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                           const float* img_target, const float* l1_weight, const float* ssim_mask, float* maps_ws,
+                           float* partials, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !img_target || !maps_ws || !partials))
+        return fail(EXA_RASTER_E_NULLPTR, "photo loss: NULL argument");
+    return launch_photo_loss(B, C, H, W, crop, img_out, img_target, l1_weight, ssim_mask, 0.f, 0.f, maps_ws, partials,
+                             nullptr, 0, stream, "photo_stats");
+}
+
+int exa_photo_loss_grad(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                        const float* img_target, const float* l1_weight, const float* ssim_mask, float w_l1, float w_ssim,
+                        const float* maps_ws, float* dL_dimg, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !img_target || !maps_ws || !dL_dimg))
+        return fail(EXA_RASTER_E_NULLPTR, "photo loss: NULL argument");
+    return launch_photo_loss(B, C, H, W, crop, img_out, img_target, l1_weight, ssim_mask, w_l1, w_ssim,
+                             const_cast<float*>(maps_ws), nullptr, dL_dimg, 1, stream, "photo_grad");
+}
+
+int exa_l1_forward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                   const float* img_target, const float* mask, const float* bg, float* l1_map, void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !img_target || !l1_map))
+        return fail(EXA_RASTER_E_NULLPTR, "l1: NULL argument");
+    return launch_l1(B, C, H, W, crop, img_out, img_target, mask, bg, nullptr, l1_map, 0, stream, "l1_fwd");
+}
+
+int exa_l1_backward(int32_t B, int32_t C, int32_t H, int32_t W, const int32_t* crop, const float* img_out,
+                    const float* img_target, const float* mask, const float* bg, const float* dL_dmap, float* dL_dimg,
+                    void* stream) {
+    int rc = check_crop(B, C, H, W, crop);
+    if (rc) return rc;
+    if ((int64_t)B * C * crop[2] * crop[3] > 0 && (!img_out || !img_target || !dL_dmap || !dL_dimg))
+        return fail(EXA_RASTER_E_NULLPTR, "l1: NULL argument");
+    return launch_l1(B, C, H, W, crop, img_out, img_target, mask, bg, dL_dmap, dL_dimg, 1, stream, "l1_bwd");
+}
+
+}  // extern "C"
