@@ -96,6 +96,12 @@ gradient w.r.t. the render, without the ``lpips`` and ``torchvision`` packages; 
 called at ``avatar/main/model.py:199,206``):
 
     from exavatar_release_amd import LPIPS, lpips_distance
+
+and for the last four regularisers of the loss block (``gaussian_mean_reg``, ``gaussian_scale_reg``, ``joint_offset_reg`` and
+``JointOffsetSymmetricReg`` as one autograd node of two launches forward and one backward, with the constant weights the
+reference rebuilds every iteration; reference ``avatar/main/model.py:217-232, 253-257``, ``avatar/common/nets/loss.py:133-146``):
+
+    from exavatar_release_amd import OffsetRegs, offset_regs, JointOffsetSymmetricReg, symmetric_joint_pairs, loss_weights
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -121,6 +127,7 @@ from .face_loss import FaceRGBLoss, face_composite, foreground_composite
 from .optim import Adam, adam_step
 from .scene_gaussian import SceneGaussian
 from .lpips import LPIPS, lpips_distance
+from .offset_regs import JointOffsetSymmetricReg, OffsetRegs, loss_weights, offset_regs, symmetric_joint_pairs
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -132,4 +139,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'ArmRGBReg', 'HandRGBReg', 'HandMeanReg', 'ArmPlan', 'arm_neighbors', 'arm_rgb_loss', 'get_arm',
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
            'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step',
-           'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance']
+           'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance',
+           'OffsetRegs', 'offset_regs', 'JointOffsetSymmetricReg', 'symmetric_joint_pairs', 'loss_weights']

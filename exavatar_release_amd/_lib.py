@@ -355,7 +355,14 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_hand_rgb_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 7),
     'exa_mesh_hand_mean_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 5),
     'exa_mesh_hand_mean_backward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 6),
-}, _by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody,
+    # the Gaussian offset and joint offset regularisers (csrc/offset_regs.hip); the pair table's arrays are host int32
+    # arrays, the backward's two cotangent arrays host arrays of device pointers
+    'exa_mesh_offset_regs_blocks': (ctypes.c_int64, [_I32, _I32]),
+    'exa_mesh_offset_regs_pair_table': (ctypes.c_int, [_I32, _I32, _IP, _IP, _IP]),
+    'exa_mesh_offset_regs_vertex_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 10),
+    'exa_mesh_offset_regs_joint_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 10),
+    'exa_mesh_offset_regs_backward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 12 + [_PP, _PP] + [c_void_p] * 6),
+},_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody,
             ExaMeshPosed))
 
 # the K-nearest-neighbour search

@@ -57,6 +57,8 @@ SOURCES = {
     'posed_body.hip': ['-ffp-contract=off'],
     # the arm and hand regularisers are defined operation by operation (include/exa_mesh.h)
     'vertex_regs.hip': ['-ffp-contract=off'],
+    # the Gaussian offset and joint offset regularisers are defined operation by operation (include/exa_mesh.h)
+    'offset_regs.hip': ['-ffp-contract=off'],
     # the scene-Gaussian stage and its backward are defined operation by operation (include/exa_raster.h)
     'scene_assets.hip': ['-ffp-contract=off'],
     # the pose-parameter stage and its backward are defined operation by operation (include/exa_mesh.h)

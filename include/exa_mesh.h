@@ -36,6 +36,10 @@
  * (avatar/common/nets/module.py:649-684) and the detached pose features of module.py:464,484,498, under
  * `exavatar_release_amd.pose_params`.
  *
+ * And the last four terms of the loss block: `exa_mesh_offset_regs_*` are the reference's `gaussian_mean_reg`,
+ * `gaussian_scale_reg`, `joint_offset_reg` and `JointOffsetSymmetricReg` (avatar/main/model.py:217-232, 253-257,
+ * avatar/common/nets/loss.py:133-146), under `exavatar_release_amd.offset_regs`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -723,6 +727,89 @@ int exa_mesh_hand_mean_forward(int32_t B, int32_t V, int32_t H, const float* off
 /* One launch.  grad_loss [dev] [B, H]; h_rank [dev] [V]; dL_doffset [dev] [B, V, 3], fully written. */
 int exa_mesh_hand_mean_backward(int32_t B, int32_t V, int32_t H, const float* offset, const float* normal,
                                 const float* grad_loss, const int32_t* h_rank, float* dL_doffset, void* stream);
+
+/* ---- Gaussian offset and joint offset regularisers (reference model.py:217-232, 253-257, loss.py:133-146) ------------
+ * The four remaining terms of the loss block: two over the B V rows of the upsampled mesh, two over the J joints.  Every
+ * operation is rounded in fp32 and never contracted; every sum runs in the order stated here.  No atomics, no memset:
+ * every output element is written by the launch that owns it.
+ *
+ * TERMS.  Row i = b V + v, channel c = 0, 1, 2; a = mean_offset, b = mean_offset_offset, z = scale, all [B, V, 3];
+ * u = scale_offset, [B, V, 1] (the one value of the row serves its three channels) or [B, V, 3]; w_mean, w_scale [V].
+ *   0  mean_map[i,c]  = ((a * a) + (b * b)) * w_mean[v]                                       N_0 = 3 B V
+ *   1  scale_map[i,c] = ((z * z) + (u * u)) * w_scale[v]                                      N_1 = 3 B V
+ * jo = joint_offset, ref = joint_ref, wj = w_joint, all [J, 3], element e = 3 j + c; pair p = (r, l) = (pair_r[p], pair_l[p]):
+ *   2  joint_map[e]   = ((jo[e] - ref[e]) * (jo[e] - ref[e])) * wj[e]                         N_2 = 3 J
+ *   3  sym_map[p]     = (|jo[r,0] + jo[l,0]| + |jo[r,1] - jo[l,1]|) + |jo[r,2] - jo[l,2]|     N_3 = n_pairs
+ *      A pair index outside [0, J) reads nothing and gives NaN.
+ *
+ * MEANS.  WG(s) is the workgroup sum of 256 threads' values s: inside each wave of 64 lanes a butterfly over the lane
+ * distances 32, 16, 8, 4, 2, 1 (s = s + s[lane ^ distance]), then ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   Terms 0, 1: the rows are cut into exa_mesh_offset_regs_blocks(B, V) = ceil(B V / 256) workgroups of
+ *       EXA_MESH_OFFSET_ROWS = 256 consecutive rows, one row per thread: row sum = (t[i,0] + t[i,1]) + t[i,2], +0.0 for a
+ *       thread past the last row; partial[k][g] = WG(row sums) of workgroup g.  Then thread j of ONE workgroup:
+ *       s = +0.0, then s = s + partial[k][j], partial[k][j + 256], .. in that order; sum_k = WG(s).
+ *   Term 2: thread j: s = +0.0, then s = s + joint_map[j], joint_map[j + 256], ..; sum_2 = WG(s).  Term 3 the same
+ *       over sym_map.
+ *   means[k] = sum_k / (float)N_k.   N_k == 0 gives 0 / 0 = NaN, as torch.mean of an empty tensor does.
+ *
+ * BACKWARD.  The cotangent of element x of term k is g = dL_dmaps[k][x], or in mean mode g = *dL_dmeans[k] * (1 / (float)N_k):
+ * the reciprocal is rounded first, as torch's backward of .mean() does on the device.  dL_dmeans[k] points to DEVICE
+ * memory: nothing is read back.
+ *   dL_dmean_offset[i,c]        = (g0 * w_mean[v]) * (2 * a)        (torch's MulBackward, then PowBackward)
+ *   dL_dmean_offset_offset[i,c] = (g0 * w_mean[v]) * (2 * b)
+ *   dL_dscale[i,c]              = (g1 * w_scale[v]) * (2 * z)
+ *   dL_dscale_offset, [B, V, 3]: (g1 * w_scale[v]) * (2 * u[i,c]);
+ *                     [B, V, 1]: r = ((g1[i,0] * w + g1[i,1] * w) + g1[i,2] * w), w = w_scale[v];  r * (2 * u[i])
+ *                                (the broadcast is summed first and the power rule applied to the sum, as torch does)
+ *   dL_djoint_offset[e] = d_reg + d_sym;   d_reg = (g2 * wj[e]) * (2 * (jo[e] - ref[e]));   for the pair p of joint j,
+ *       found through joint_pair[j] = 2 p + side (side 0: j = pair_r[p], 1: j = pair_l[p]; -1: in no pair), with
+ *       sign(x) = (x > 0) - (x < 0), so sign(0) = 0:
+ *         c = 0:     d_sym = sign(jo[r,0] + jo[l,0]) * g3            on either side
+ *         c = 1, 2:  d_sym = sign(jo[r,c] - jo[l,c]) * g3            on the right side, its negation on the left
+ *       A joint in no pair gets d_reg alone, and d_sym alone where term 2 has no cotangent.
+ * A term without a cotangent (its entry NULL) contributes nothing: the gradients that only it reaches are written +0.0.
+ * Every requested gradient is written whole; the caller clears nothing. */
+#define EXA_MESH_OFFSET_ROWS 256        /* rows per workgroup of the vertex launch = rows per partial */
+
+/* The partials per term of the vertex launch in mean mode: ceil(B V / 256); 0 for an empty or invalid shape. */
+int64_t exa_mesh_offset_regs_blocks(int32_t B, int32_t V);
+
+/* Host only.  pair_r, pair_l [host] [n_pairs]: checks every index against [0, J) and that no joint is named twice
+ * (EXA_MESH_E_INVALID), and writes joint_pair [host] [J], the inverse table the backward reads. */
+int exa_mesh_offset_regs_pair_table(int32_t J, int32_t n_pairs, const int32_t* pair_r, const int32_t* pair_l,
+                                    int32_t* joint_pair);
+
+/* One launch: terms 0 and 1.  mean_offset, mean_offset_offset, scale [dev] [B, V, 3]; scale_offset [dev]
+ * [B, V, scale_offset_channels], 1 or 3 channels; w_mean, w_scale [dev] [V].  Map mode: mean_map, scale_map [dev]
+ * [B, V, 3], fully written, partials NULL.  Mean mode: both maps NULL, partials [dev] [2, exa_mesh_offset_regs_blocks],
+ * fully written.  Both or neither is EXA_MESH_E_INVALID.  B V == 0 is a successful no-op. */
+int exa_mesh_offset_regs_vertex_forward(int32_t B, int32_t V, int32_t scale_offset_channels, const float* mean_offset,
+                                        const float* mean_offset_offset, const float* scale, const float* scale_offset,
+                                        const float* w_mean, const float* w_scale, float* mean_map, float* scale_map,
+                                        float* partials, void* stream);
+
+/* One launch of one workgroup: terms 2 and 3 and, in mean mode, the four means.  joint_offset, joint_ref, w_joint [dev]
+ * [J, 3]; pair_r, pair_l [dev] [n_pairs] int32, n_pairs <= J / 2.  Map mode: joint_map [dev] [J, 3] and sym_map [dev]
+ * [n_pairs], fully written, means NULL.  Mean mode: both maps NULL, partials [dev] the vertex launch's for the same
+ * B, V (not read when B V == 0), means [dev] [4], fully written.  Both or neither is EXA_MESH_E_INVALID. */
+int exa_mesh_offset_regs_joint_forward(int32_t B, int32_t V, int32_t J, int32_t n_pairs, const float* joint_offset,
+                                       const float* joint_ref, const float* w_joint, const int32_t* pair_r,
+                                       const int32_t* pair_l, float* joint_map, float* sym_map, const float* partials,
+                                       float* means, void* stream);
+
+/* One launch.  The inputs as in the forward; joint_pair [dev] [J] the table of exa_mesh_offset_regs_pair_table.
+ * dL_dmaps, dL_dmeans: HOST arrays of four device pointers, indexed by term; either may be NULL, and so may any entry.
+ * Entries of both kinds, or no entry at all, is EXA_MESH_E_INVALID.  dL_dmaps[k] has the shape of term k's map;
+ * dL_dmeans[k] points to one float.  The five gradients [dev] have the shapes of their inputs; a NULL one is not
+ * computed, and with none left to write there is no launch.  Inputs that no requested gradient reads may be NULL. */
+int exa_mesh_offset_regs_backward(int32_t B, int32_t V, int32_t scale_offset_channels, int32_t J, int32_t n_pairs,
+                                  const float* mean_offset, const float* mean_offset_offset, const float* scale,
+                                  const float* scale_offset, const float* w_mean, const float* w_scale,
+                                  const float* joint_offset, const float* joint_ref, const float* w_joint,
+                                  const int32_t* pair_r, const int32_t* pair_l, const int32_t* joint_pair,
+                                  const float* const* dL_dmaps, const float* const* dL_dmeans, float* dL_dmean_offset,
+                                  float* dL_dmean_offset_offset, float* dL_dscale, float* dL_dscale_offset,
+                                  float* dL_djoint_offset, void* stream);
 
 #ifdef __cplusplus
 }
