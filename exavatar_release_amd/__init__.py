@@ -102,6 +102,12 @@ and for the last four regularisers of the loss block (``gaussian_mean_reg``, ``g
 reference rebuilds every iteration; reference ``avatar/main/model.py:217-232, 253-257``, ``avatar/common/nets/loss.py:133-146``):
 
     from exavatar_release_amd import OffsetRegs, offset_regs, JointOffsetSymmetricReg, symmetric_joint_pairs, loss_weights
+
+and for the face texture that ``MeshRenderer`` samples (``XY2UV`` and ``get_face_index_map_uv`` with pytorch3d's
+``OrthographicCameras``, the accumulation of ``unwrap.py`` and the region mask of ``make_uv_mask``; forward only; reference
+``fitting/common/nets/layer.py:9-23, 41-102``, ``fitting/main/unwrap.py:76-91``, ``fitting/common/utils/flame.py:46-73``):
+
+    from exavatar_release_amd import XY2UV, get_face_index_map_uv, TextureUnwrap, uv_region_mask
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -128,6 +134,7 @@ from .optim import Adam, adam_step
 from .scene_gaussian import SceneGaussian
 from .lpips import LPIPS, lpips_distance
 from .offset_regs import JointOffsetSymmetricReg, OffsetRegs, loss_weights, offset_regs, symmetric_joint_pairs
+from .unwrap import XY2UV, TextureUnwrap, get_face_index_map_uv, uv_region_mask
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -140,4 +147,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'scene_assets', 'SMPLXParamDict', 'pose_params', 'pose_features', 'PosedBody',
            'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step',
            'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance',
-           'OffsetRegs', 'offset_regs', 'JointOffsetSymmetricReg', 'symmetric_joint_pairs', 'loss_weights']
+           'OffsetRegs', 'offset_regs', 'JointOffsetSymmetricReg', 'symmetric_joint_pairs', 'loss_weights',
+           'XY2UV', 'get_face_index_map_uv', 'TextureUnwrap', 'uv_region_mask']

@@ -139,6 +139,15 @@ class ExaMeshShading(ctypes.Structure):
                 ('background', ctypes.c_float * 3)]
 
 
+class ExaMeshUnwrap(ctypes.Structure):
+    """One face-texture unwrap (include/exa_mesh.h); every pointer is a device pointer."""
+    _fields_ = [('B', ctypes.c_int32), ('V', ctypes.c_int32), ('F', ctypes.c_int32), ('C', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('Hu', ctypes.c_int32), ('Wu', ctypes.c_int32),
+                ('img', c_void_p), ('verts', c_void_p), ('faces', c_void_p), ('focal', c_void_p), ('princpt', c_void_p),
+                ('pix_to_face_xy', c_void_p), ('pix_to_face_uv', c_void_p), ('bary_uv', c_void_p),
+                ('uv_weight', c_void_p), ('face_valid', c_void_p)]
+
+
 class ExaMeshUpsample(ctypes.Structure):
     """The flat plan of one or two subdivision rounds (include/exa_mesh.h); the arrays are device pointers."""
     _fields_ = [('levels', ctypes.c_int32), ('V0', ctypes.c_int32), ('V1', ctypes.c_int32), ('Vn', ctypes.c_int32),
@@ -316,6 +325,10 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_vertex_normals': (ctypes.c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exa_mesh_forward_shaded': (ctypes.c_int, [_GP, _SHP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
+    # the face-texture unwrap: the UV-space raster (csrc/mesh_raster.hip) and the unwrap itself (csrc/unwrap.hip)
+    'exa_mesh_forward_ortho': (ctypes.c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exa_mesh_unwrap_workspace_size': (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_U64)]),
+    'exa_mesh_unwrap': (ctypes.c_int, [ctypes.POINTER(ExaMeshUnwrap), c_void_p, _U64] + [c_void_p] * 5),
     # the mesh Laplacian regulariser (csrc/mesh_reg.hip)
     'exa_mesh_neighbor_transpose': (ctypes.c_int, [_I32, _I32, c_void_p, c_void_p, c_void_p]),
     'exa_mesh_laplacian_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 8),
@@ -362,8 +375,8 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_offset_regs_vertex_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 10),
     'exa_mesh_offset_regs_joint_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 10),
     'exa_mesh_offset_regs_backward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 12 + [_PP, _PP] + [c_void_p] * 6),
-},_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUpsample, ExaMeshBody,
-            ExaMeshPosed))
+},_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUnwrap, ExaMeshUpsample,
+            ExaMeshBody, ExaMeshPosed))
 
 # the K-nearest-neighbour search
 KNN = Abi('exa_knn', 'exa_knn.h', 100, {
@@ -469,6 +482,10 @@ def laplacian_workspace_size(B, V, C):
 
 def hand_rgb_workspace_size(B, N):
     return size_query(MESH, 'exa_mesh_hand_rgb_workspace_size', B, N)
+
+
+def unwrap_workspace_size(B, F):
+    return size_query(MESH, 'exa_mesh_unwrap_workspace_size', B, F)
 
 
 def blend_workspace_size(K, N):

@@ -13,6 +13,8 @@
 //                    walks the surviving faces in index order and keeps the nearest (strict <, so the lower index wins
 //                    a tie).  Writes pix_to_face, zbuf, bary and -- TEX -- samples the texture into the NCHW render,
 //                    or -- SHADE -- Phong-shades the nearest face into the NHWC image (no barycentrics written out).
+//                    ORTHO (exa_mesh_forward_ortho, the UV-space raster of the texture unwrap): mesh_prep takes x, y as
+//                    they are, and the fragment carries the plain screen barycentrics and their blend of the depths.
 //   mesh_vertex_normals  one thread per (mesh, vertex): sums its corners' edge cross products in CSR order, normalises.
 //   mesh_bwd_faces   one wave per (mesh, face): walks the face's bbox, keeps the pixels whose pix_to_face is this face,
 //                    chains dL/d(bary, zbuf[, render]) to the three corners' camera-space xyz, sums per lane in pixel
@@ -87,6 +89,20 @@ __device__ __forceinline__ void perspective(const FaceRec& r, Bary& q) {
     q.z = q.p[0] * r.z[0] + q.p[1] * r.z[1] + q.p[2] * r.z[2];
 }
 
+// The barycentrics a fragment carries.  pytorch3d corrects for perspective only under a perspective camera: with ORTHO
+// (exa_mesh_forward_ortho) they are the plain screen barycentrics, and z their blend of the corners' depths.
+template <bool ORTHO>
+__device__ __forceinline__ void interpolate(const FaceRec& r, Bary& q) {
+    if constexpr (ORTHO) {
+        q.p[0] = q.b[0];
+        q.p[1] = q.b[1];
+        q.p[2] = q.b[2];
+        q.z = q.p[0] * r.z[0] + q.p[1] * r.z[1] + q.p[2] * r.z[2];
+    } else {
+        perspective(r, q);
+    }
+}
+
 // F.grid_sample(flip(map, rows), 2 * uv - 1, bilinear, border, align_corners=True) at one pixel: coordinates and weights.
 struct Sample {
     float ix, iy;                // clipped source coordinates in the flipped map
@@ -136,6 +152,7 @@ struct Params {
     FaceRec* recs;
     uint32_t* bins;
     int cx, cells, words;
+    int ortho;                               // verts hold screen x, y in pixels and the depth: no projection, no focal / princpt
     // outputs / gradients
     int64_t* pix_to_face;
     float* zbuf;
@@ -171,8 +188,11 @@ __global__ void __launch_bounds__(BLOCK) mesh_prep(Params P) {
     r.pad[0] = r.pad[1] = 0.f;
     // projected in fp64 and stored relative to the face's integer bbox origin: the edge functions then subtract small,
     // exactly representable numbers, and a thin face 500 px off the principal point keeps fp32's relative precision
-    const double fx = P.focal[2 * n], fy = P.focal[2 * n + 1];
-    const double cx = P.princpt[2 * n], cy = P.princpt[2 * n + 1];
+    double fx = 1.0, fy = 1.0, cx = 0.0, cy = 0.0;
+    if (!P.ortho) {
+        fx = P.focal[2 * n]; fy = P.focal[2 * n + 1];
+        cx = P.princpt[2 * n]; cy = P.princpt[2 * n + 1];
+    }
     double sx[3], sy[3];
     bool ok = true;
     for (int k = 0; k < 3; ++k) {
@@ -185,8 +205,8 @@ __global__ void __launch_bounds__(BLOCK) mesh_prep(Params P) {
         }
         const float* p = P.verts + ((size_t)n * P.V + v) * 3;
         const float Z = p[2];
-        sx[k] = fx * ((double)p[0] / Z) + cx;
-        sy[k] = fy * ((double)p[1] / Z) + cy;
+        sx[k] = P.ortho ? (double)p[0] : fx * ((double)p[0] / Z) + cx;
+        sy[k] = P.ortho ? (double)p[1] : fy * ((double)p[1] / Z) + cy;
         r.z[k] = Z;
         ok = ok && Z > MIN_Z && isfinite(sx[k]) && isfinite(sy[k]) && isfinite(Z);
     }
@@ -258,7 +278,7 @@ __device__ __forceinline__ void phong(const ExaMeshShading& sh, const float pos[
                  sh.material_specular[c] * (sh.light_specular[c] * spec);
 }
 
-template <bool TEX, bool SHADE = false>
+template <bool TEX, bool SHADE = false, bool ORTHO = false>
 __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
     __shared__ uint32_t s_mask[BLOCK];
     __shared__ uint64_t s_nz[BLOCK / 64];
@@ -307,7 +327,7 @@ __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
                     if (bb[0] > 0.f && bb[1] > 0.f && bb[2] > 0.f) {
                         Bary qb;
                         qb.b[0] = bb[0]; qb.b[1] = bb[1]; qb.b[2] = bb[2];
-                        perspective(r, qb);
+                        interpolate<ORTHO>(r, qb);
                         if (qb.z < bz) {          // faces arrive in index order: strict < keeps the lower index on a tie
                             bz = qb.z;
                             best = f;
@@ -324,7 +344,7 @@ __global__ void __launch_bounds__(BLOCK) mesh_raster_fwd(Params P) {
     if (best >= 0) {
         const FaceRec r = recs[best];
         screen_bary(r, px - (float)r.bx0, py - (float)r.by0, qb.b);
-        perspective(r, qb);
+        interpolate<ORTHO>(r, qb);
     }
     if (!SHADE || P.pix_to_face) P.pix_to_face[pix] = best >= 0 ? (int64_t)n * P.F + best : -1;
     if (P.zbuf) P.zbuf[pix] = best >= 0 ? qb.z : -1.f;
@@ -536,7 +556,7 @@ int check_shape(int32_t N, int32_t V, int32_t F, int32_t H, int32_t W) {
     return 0;
 }
 
-int fill(const ExaMeshGeometry* g, const ExaMeshTexture* tex, Params& P) {
+int fill(const ExaMeshGeometry* g, const ExaMeshTexture* tex, Params& P, bool ortho = false) {
     if (!g) return fail(EXA_MESH_E_NULLPTR, "geometry is NULL");
     if (int rc = check_shape(g->N, g->V, g->F, g->H, g->W)) return rc;
     memset(&P, 0, sizeof(P));
@@ -547,8 +567,10 @@ int fill(const ExaMeshGeometry* g, const ExaMeshTexture* tex, Params& P) {
     P.words = words_of(g->F);
     if (g->N > 0 && g->F > 0) {
         if (g->V > 0 && !g->verts) return fail(EXA_MESH_E_NULLPTR, "verts is NULL");
-        if (!g->faces || !g->focal || !g->princpt) return fail(EXA_MESH_E_NULLPTR, "faces / focal / princpt is NULL");
+        if (!g->faces || (!ortho && (!g->focal || !g->princpt)))
+            return fail(EXA_MESH_E_NULLPTR, "faces / focal / princpt is NULL");
     }
+    P.ortho = ortho ? 1 : 0;
     if (tex) {
         if (tex->C < 1 || tex->C > EXA_MESH_MAX_CHANNELS) return fail(EXA_MESH_E_INVALID, "texture channels must be 1 .. 8");
         if (tex->tex_H < 1 || tex->tex_W < 1 || tex->tex_H > 65536 || tex->tex_W > 65536)
@@ -628,6 +650,23 @@ int exa_mesh_forward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, void* 
     else
         hipLaunchKernelGGL(mesh_raster_fwd<false>, grid, dim3(BLOCK), 0, st, P);
     return launched("mesh_raster_fwd");
+}
+
+int exa_mesh_forward_ortho(const ExaMeshGeometry* g, void* face_ws, void* bin_ws, int64_t* pix_to_face, float* zbuf,
+                           float* bary, void* stream) {
+    Params P;
+    if (int rc = fill(g, nullptr, P, true)) return rc;
+    const int64_t npix = (int64_t)P.N * P.H * P.W;
+    if (npix == 0) return 0;
+    if (!pix_to_face) return fail(EXA_MESH_E_NULLPTR, "pix_to_face is NULL");
+    if (P.F > 0 && (!face_ws || !bin_ws)) return fail(EXA_MESH_E_NULLPTR, "workspace is NULL");
+    P.recs = static_cast<FaceRec*>(face_ws);
+    P.bins = static_cast<uint32_t*>(bin_ws);
+    P.pix_to_face = pix_to_face; P.zbuf = zbuf; P.bary = bary;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = launch_prep_bin(P, st)) return rc;
+    hipLaunchKernelGGL((mesh_raster_fwd<false, false, true>), raster_grid(P), dim3(BLOCK), 0, st, P);
+    return launched("mesh_raster_fwd (ortho)");
 }
 
 int exa_mesh_backward(const ExaMeshGeometry* g, const ExaMeshTexture* tex, const void* face_ws,

@@ -40,6 +40,11 @@
  * `gaussian_scale_reg`, `joint_offset_reg` and `JointOffsetSymmetricReg` (avatar/main/model.py:217-232, 253-257,
  * avatar/common/nets/loss.py:133-146), under `exavatar_release_amd.offset_regs`.
  *
+ * And the face texture that the face render samples: `exa_mesh_forward_ortho` is the same raster under pytorch3d's
+ * `OrthographicCameras` (the reference's `get_face_index_map_uv`, fitting/common/nets/layer.py:9-23) and
+ * `exa_mesh_unwrap` the reference's `XY2UV.forward` with the accumulation of fitting/main/unwrap.py:76-83
+ * (layer.py:41-102), under `exavatar_release_amd.unwrap`.  Forward only.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -161,6 +166,78 @@ int exa_mesh_vertex_normals(const ExaMeshGeometry* g, const int32_t* vert_offset
  *   image            [dev] [N, H, W, 3] (channel-last): the shaded colour, `background` at empty pixels (required). */
 int exa_mesh_forward_shaded(const ExaMeshGeometry* g, const ExaMeshShading* shading, const float* normals, void* face_ws,
                             void* bin_ws, int64_t* pix_to_face, float* zbuf, float* image, void* stream);
+
+/* ---- Face-texture unwrap (reference XY2UV and get_face_index_map_uv, fitting/common/nets/layer.py:9-23, 41-102) -----
+ * Forward only: nothing in the reference differentiates through the unwrap.
+ *
+ * exa_mesh_forward_ortho is exa_mesh_forward under pytorch3d's OrthographicCameras(in_ndc=False) with focal 1 and
+ * principal point 0: x and y of `verts` are screen coordinates in pixels (the centre of pixel (row i, col j) lies at
+ * (j + 0.5, i + 0.5)), z is the depth; g->focal and g->princpt are ignored and may be NULL.  Coverage, the degenerate-face
+ * rule, the z <= 1e-6 cull and the tie rule are exa_mesh_forward's.  pytorch3d corrects barycentrics for perspective only
+ * under a perspective camera, so `bary` holds the plain screen barycentrics b_k = E_k / A and
+ * zbuf = (b_0 z_0 + b_1 z_1) + b_2 z_2; -1 at background pixels in all three outputs.  The reference's UV raster is this call
+ * on (u * W, v * H, 1).  Same workspaces as exa_mesh_forward; zbuf and bary may be NULL. */
+int exa_mesh_forward_ortho(const ExaMeshGeometry* g, void* face_ws, void* bin_ws, int64_t* pix_to_face, float* zbuf,
+                           float* bary, void* stream);
+
+/* One unwrap: B images [B, C, H, W] sampled into B maps [B, C, Hu, Wu] through a mesh of V vertices and F faces.
+ *
+ * VISIBLE FACES.  Face f of item n is visible when some pixel of pix_to_face_xy[n] holds n * F + f (the packed index
+ * exa_mesh_forward writes).  The reference's wrap-around is reproduced: its torch.unique keeps the -1 of background
+ * pixels and `valid_face_mask[-1] = 1` then marks the LAST face, so when item n has at least one background pixel, face
+ * F - 1 is visible whether it was hit or not.  A value outside {-1} and [n F, (n + 1) F) marks nothing.
+ *
+ * TEXELS.  Texel t = (row, col) of the map holds face f = pix_to_face_uv[t] and barycentrics b = bary_uv[t] (item 0 of
+ * an exa_mesh_forward_ortho of the UV atlas: f is an index into `faces`).  Where f is -1 (or outside [0, F)), or face f of
+ * item n is not visible: value = +0.0 and mask = 0 in every channel (the reference has -0.0 there).  Otherwise, with
+ * (X_k, Y_k, Z_k) = verts[n, faces[f, k]], every operation rounded in fp32, never contracted, in this order:
+ *   x_k = (X_k / Z_k) * fx + cx,   y_k = (Y_k / Z_k) * fy + cy                        (fx, fy) = focal[n], (cx, cy) = princpt[n]
+ *   px  = (x_0 b_0 + x_1 b_1) + x_2 b_2,   py likewise
+ *   gx  = ((px / (float)(W - 1)) * 2) - 1,   gy = ((py / (float)(H - 1)) * 2) - 1
+ *   ix  = ((gx + 1) / 2) * (float)(W - 1),   iy = ((gy + 1) / 2) * (float)(H - 1)      F.grid_sample, align_corners=True
+ *   x0 = floor(ix), y0 = floor(iy);  nw = ((x0 + 1) - ix) * ((y0 + 1) - iy),  ne = (ix - x0) * ((y0 + 1) - iy),
+ *   sw = ((x0 + 1) - ix) * (iy - y0),  se = (ix - x0) * (iy - y0)
+ *   v = +0.0; v = v + img(y0, x0) * nw; v = v + img(y0, x0 + 1) * ne; v = v + img(y0 + 1, x0) * sw;
+ *   v = v + img(y0 + 1, x0 + 1) * se                       a tap outside the image is skipped (padding_mode='zeros')
+ *   mask = (v != -1);  value = mask ? v : +0.0             per channel
+ * A position that is not finite (an image of one row or column divides by zero, as in the reference) has no tap inside:
+ * v = +0.0, mask = 1.  A raster-visible face has every corner at Z > 1e-6.  The wrap-around can mark a last face that the
+ * raster culled; where one of its corners has Z <= 1e-6 the reference samples through a mirrored or non-finite
+ * projection, and this call writes value = +0.0 and mask = 0 instead: the one deliberate difference.
+ *
+ * ACCUMULATION (reference fitting/main/unwrap.py:76-83), when tex_sum is given: one thread owns a texel and adds the items
+ * in index order, so there are no atomics and the same inputs give the same bits:
+ *   tex_sum[c, t]  = tex_sum[c, t]  + (value[n, c, t] * uv_weight[t]) * face_valid[n]           n = 0 .. B - 1
+ *   mask_sum[c, t] = mask_sum[c, t] + ((float)mask[n, c, t] * uv_weight[t]) * face_valid[n]
+ * in place.  uvmap and mask may then be NULL (no [B, C, Hu, Wu] array is written). */
+typedef struct ExaMeshUnwrap {
+    int32_t B, V, F, C;                 /* items, vertices per item, faces, channels (1 .. EXA_MESH_MAX_CHANNELS) */
+    int32_t H, W;                       /* image rows, columns */
+    int32_t Hu, Wu;                     /* map rows, columns */
+    const float* img;                   /* [dev] [B, C, H, W] */
+    const float* verts;                 /* [dev] [B, V, 3] camera space */
+    const int32_t* faces;               /* [dev] [F, 3] */
+    const float* focal;                 /* [dev] [B, 2] */
+    const float* princpt;               /* [dev] [B, 2] */
+    const int64_t* pix_to_face_xy;      /* [dev] [B, H, W]: exa_mesh_forward's of the same verts at H x W (an INPUT) */
+    const int64_t* pix_to_face_uv;      /* [dev] [Hu, Wu] */
+    const float* bary_uv;               /* [dev] [Hu, Wu, 3] */
+    const float* uv_weight;             /* [dev] [Hu, Wu]; required with tex_sum, else ignored */
+    const float* face_valid;            /* [dev] [B] or NULL (every item counts 1); read with tex_sum only */
+} ExaMeshUnwrap;
+
+/* Bytes of the visibility flags ([B, F], one byte each, rounded up to 256). */
+int exa_mesh_unwrap_workspace_size(int32_t B, int32_t F, uint64_t* out_bytes);
+
+/* Three launches: the flags are cleared by a kernel of the library's (no memset), marked by one thread per image pixel
+ * (every writer stores the same byte: no atomics), and one thread per texel writes all items and channels.
+ *   flag_ws            [dev] of ws_bytes >= exa_mesh_unwrap_workspace_size.
+ *   uvmap              [dev] [B, C, Hu, Wu] float, fully written; mask [dev] [B, C, Hu, Wu] bytes (0 / 1), fully written.
+ *                      Both or neither; required without tex_sum.
+ *   tex_sum, mask_sum  [dev] [C, Hu, Wu] float, updated in place; both or neither.
+ * B == 0 or Hu * Wu == 0 is a successful no-op. */
+int exa_mesh_unwrap(const ExaMeshUnwrap* u, void* flag_ws, uint64_t ws_bytes, float* uvmap, uint8_t* mask,
+                    float* tex_sum, float* mask_sum, void* stream);
 
 /* ---- Mesh Laplacian regulariser (reference LaplacianReg) ------------------------------------------------------------
  * x [B, V, C] fp32 (1 <= C <= EXA_MESH_LAP_MAX_CHANNELS), a neighbour table nbr_idx [V, K] int32 / nbr_w [V, K] fp32
