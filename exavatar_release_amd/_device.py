@@ -120,6 +120,33 @@ def check_tensor(what, name, x, f32=True, rocm=False, on=None):
         raise ValueError('%s: %s is not on the device of %s' % (what, name, on[1]))
 
 
+def check_shape(what, name, x, shape, text):
+    check_tensor(what, name, x)
+    if x.dim() != len(shape) or any(s is not None and x.shape[i] != s for i, s in enumerate(shape)):
+        raise ValueError('%s: %s must be %s (it is %s)' % (what, name, text, tuple(x.shape)))
+
+
+def check_mask(what, name, m, V):
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or m.dim() != 1 or m.shape[0] != V:
+        raise ValueError('%s: %s must be a bool [V] tensor with V = %d (it is %s)' % (
+            what, name, V, '%s %s' % (m.dtype, tuple(m.shape)) if isinstance(m, torch.Tensor) else type(m).__name__))
+
+
+def check_devices(what, anchor_name, anchor, **others):
+    """The anchor is on a ROCm device (a ValueError here, unlike ``need_rocm``), the others (None passes) on the anchor's."""
+    if anchor.device.type != 'cuda':
+        raise ValueError('%s: %s must be on a ROCm device (it is on %s; there is no CPU path)'
+                         % (what, anchor_name, anchor.device))
+    for name, x in others.items():
+        if x is not None and x.device != anchor.device:
+            raise ValueError('%s: %s is not on the device of %s' % (what, name, anchor_name))
+
+
+def check_reduce(what, reduce):
+    if reduce not in (None, 'mean'):
+        raise ValueError("%s: reduce must be None or 'mean' (it is %r)" % (what, reduce))
+
+
 def check_no_grad(what, name, x, kind='data'):
     """What the reference holds as ``kind`` (data, a buffer, camera data) gets no gradient: a tensor that requires one is
     refused.  Anything else passes (None included)."""

@@ -218,32 +218,25 @@ def pose_constants(pose, posedirs=None):
     return f32(rot), f32(offsets), f32(rot_inverse)
 
 
-class BodyTemplate(nn.Module):
-    """The shaped SMPL-X template in the big pose and the zero pose (module docstring).
+_f32 = lambda x: x.detach().to(torch.float32)      # noqa: E731
 
-    ``v_template`` [V, 3], ``shape_dirs`` [V, 3, L] (1 <= L <= 512; concatenate ``expr_dirs`` behind ``shapedirs`` if
-    expression coefficients are wanted), ``J_regressor`` [J, V], ``lbs_weights`` [V, J] (J <= 64), ``parents`` a sequence
-    or CPU tensor of J ints, ``upsampler`` a ``MeshUpsampler`` over the template's faces, ``rot_pose`` and
-    ``rot_inverse`` [J, 3, 3], ``pose_offsets`` and ``face_offset`` [V, 3] or None.  All of them are data
-    (float32): a tensor that requires a gradient is refused.  The re-laid tables are non-persistent buffers, so
-    ``state_dict`` does not change; the sparse ``J_regressor`` is compacted once to its non-zeros."""
 
-    def __init__(self, v_template, shape_dirs, J_regressor, lbs_weights, parents, upsampler, *, rot_pose, rot_inverse,
-                 pose_offsets=None, face_offset=None, root_joint_idx=0):
-        super(BodyTemplate, self).__init__()
-        what = 'BodyTemplate'
-        named = (('v_template', v_template), ('shape_dirs', shape_dirs), ('J_regressor', J_regressor),
-                 ('lbs_weights', lbs_weights), ('rot_pose', rot_pose), ('rot_inverse', rot_inverse),
-                 ('pose_offsets', pose_offsets), ('face_offset', face_offset))
-        for name, x in named:
-            if x is None and name in ('pose_offsets', 'face_offset'):
+class _SmplxTables(nn.Module):
+    """What ``BodyTemplate`` and ``PosedBody`` (posed_body.py) share: the checks of the data tensors and of the five
+    tables' shapes, the re-laid non-persistent buffers, the head of ``from_layer`` and the cache of the C descriptor."""
+
+    def _check_data(self, what, named):
+        """``named``: (name, float32 data tensor on ``v_template``'s device, may be None) entries, ``v_template`` first."""
+        for name, x, optional in named:
+            if x is None and optional:
                 continue
             check_tensor(what, name, x)
             check_no_grad(what, name, x)
-            if x.device != v_template.device:
+            if x.device != named[0][1].device:
                 raise ValueError('%s: %s is not on the device of v_template' % (what, name))
-        if not isinstance(upsampler, MeshUpsampler):
-            raise TypeError('%s: upsampler must be a MeshUpsampler' % what)
+
+    def _check_tables(self, what, v_template, shape_dirs, J_regressor, parents, lbs_weights):
+        """The shape checks of the five tables, in this order; sets ``_parents`` and the three sizes, returns (V, L, J)."""
         if v_template.dim() != 2 or v_template.shape[1] != 3 or v_template.shape[0] < 1:
             raise ValueError('%s: v_template must be [V, 3] (it is %s)' % (what, tuple(v_template.shape)))
         V = v_template.shape[0]
@@ -260,6 +253,75 @@ class BodyTemplate(nn.Module):
             raise ValueError('%s: parents names %d joints, J_regressor %d' % (what, len(self._parents), J))
         if tuple(lbs_weights.shape) != (V, J):
             raise ValueError('%s: lbs_weights must be [V, J] = [%d, %d] (it is %s)' % (what, V, J, tuple(lbs_weights.shape)))
+        self.num_verts, self.num_coef, self.num_joints = V, L, J
+        return V, L, J
+
+    def _register_tables(self, v_template, face_offset, shape_dirs, own, J_regressor, lbs_weights):
+        """The non-persistent buffers, in this order: ``v_base``, ``dirs``, the class's ``own`` (name, tensor or None),
+        the regressor's non-zeros as a CSR (``jreg_*``), its transpose's (``jregT_*``) and ``weights``; sets ``nnz``."""
+        V, L = self.num_verts, self.num_coef
+        i32 = lambda x: x.to(torch.int32).contiguous()      # noqa: E731
+        buf = lambda name, x: self.register_buffer(name, x, persistent=False)      # noqa: E731
+        buf('v_base', (v_template if face_offset is None else v_template + face_offset).contiguous().clone())
+        buf('dirs', shape_dirs.reshape(3 * V, L).t().contiguous())                   # feature-major [L, 3 V]
+
+        def csr(prefix, index, m):
+            nz = torch.nonzero(m, as_tuple=False)                                    # ascending (row, column)
+            counts = torch.bincount(nz[:, 0], minlength=m.shape[0])
+            buf(prefix + '_off', i32(torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))))
+            buf(prefix + '_' + index, i32(nz[:, 1]))
+            buf(prefix + '_val', m[nz[:, 0], nz[:, 1]].contiguous())
+            return int(nz.shape[0])
+
+        for name, x in own:
+            buf(name, x)
+        self.nnz = csr('jreg', 'col', J_regressor)
+        csr('jregT', 'row', J_regressor.t())
+        buf('weights', lbs_weights.contiguous().clone())
+        self._desc = None
+
+    @staticmethod
+    def _layer_tables(smplx_layer):
+        """(``v_template``, ``cat(shapedirs, expr_dirs)``, ``parents`` as a list) of a smplx layer, float32."""
+        dirs = [_f32(smplx_layer.shapedirs)]
+        if getattr(smplx_layer, 'expr_dirs', None) is not None:
+            dirs.append(_f32(smplx_layer.expr_dirs))
+        parents = smplx_layer.parents
+        parents = parents.tolist() if isinstance(parents, torch.Tensor) else list(parents)
+        return _f32(smplx_layer.v_template), torch.cat(dirs, 2), parents
+
+    def _cached_descriptor(self, key, sizes, make):
+        """(the C descriptor, forward workspace bytes, backward workspace bytes), rebuilt when ``key`` (the buffers' data
+        pointers) changed: ``make(p)`` builds the struct, ``p(t)`` a buffer's address or None; ``sizes`` names the size query."""
+        if self._desc is None or self._desc[0] != key:
+            d = make(lambda t: None if t is None else (t.data_ptr() or None))
+            fwd, bwd = ctypes.c_uint64(), ctypes.c_uint64()
+            _lib.MESH.check(getattr(_lib.load(), sizes)(ctypes.byref(d), ctypes.byref(fwd), ctypes.byref(bwd)))
+            self._desc = (key, d, int(fwd.value), int(bwd.value))
+        return ctypes.byref(self._desc[1]), self._desc[2], self._desc[3]
+
+
+class BodyTemplate(_SmplxTables):
+    """The shaped SMPL-X template in the big pose and the zero pose (module docstring).
+
+    ``v_template`` [V, 3], ``shape_dirs`` [V, 3, L] (1 <= L <= 512; concatenate ``expr_dirs`` behind ``shapedirs`` if
+    expression coefficients are wanted), ``J_regressor`` [J, V], ``lbs_weights`` [V, J] (J <= 64), ``parents`` a sequence
+    or CPU tensor of J ints, ``upsampler`` a ``MeshUpsampler`` over the template's faces, ``rot_pose`` and
+    ``rot_inverse`` [J, 3, 3], ``pose_offsets`` and ``face_offset`` [V, 3] or None.  All of them are data
+    (float32): a tensor that requires a gradient is refused.  The re-laid tables are non-persistent buffers, so
+    ``state_dict`` does not change; the sparse ``J_regressor`` is compacted once to its non-zeros."""
+
+    def __init__(self, v_template, shape_dirs, J_regressor, lbs_weights, parents, upsampler, *, rot_pose, rot_inverse,
+                 pose_offsets=None, face_offset=None, root_joint_idx=0):
+        super(BodyTemplate, self).__init__()
+        what = 'BodyTemplate'
+        self._check_data(what, (('v_template', v_template, False), ('shape_dirs', shape_dirs, False),
+                                ('J_regressor', J_regressor, False), ('lbs_weights', lbs_weights, False),
+                                ('rot_pose', rot_pose, False), ('rot_inverse', rot_inverse, False),
+                                ('pose_offsets', pose_offsets, True), ('face_offset', face_offset, True)))
+        if not isinstance(upsampler, MeshUpsampler):
+            raise TypeError('%s: upsampler must be a MeshUpsampler' % what)
+        V, _, J = self._check_tables(what, v_template, shape_dirs, J_regressor, parents, lbs_weights)
         for name, x in (('rot_pose', rot_pose), ('rot_inverse', rot_inverse)):
             if tuple(x.shape) != (J, 3, 3):
                 raise ValueError('%s: %s must be [J, 3, 3] with J = %d (it is %s)' % (what, name, J, tuple(x.shape)))
@@ -271,29 +333,13 @@ class BodyTemplate(nn.Module):
         if upsampler.num_coarse != V:
             raise ValueError('%s: the upsampler is planned for %d vertices, v_template has %d'
                              % (what, upsampler.num_coarse, V))
-        self.num_verts, self.num_coef, self.num_joints, self.root_joint_idx = V, L, J, int(root_joint_idx)
+        self.root_joint_idx = int(root_joint_idx)
         self.upsampler = upsampler
-        i32 = lambda x: x.to(torch.int32).contiguous()      # noqa: E731
-        buf = lambda name, x: self.register_buffer(name, x, persistent=False)      # noqa: E731
-        buf('v_base', (v_template if face_offset is None else v_template + face_offset).contiguous().clone())
-        buf('dirs', shape_dirs.reshape(3 * V, L).t().contiguous())                   # feature-major [L, 3 V]
-        buf('pose_offsets', None if pose_offsets is None else pose_offsets.contiguous().clone())
-        nz = torch.nonzero(J_regressor, as_tuple=False)                              # ascending (joint, vertex)
-        self.nnz = int(nz.shape[0])
-        counts = torch.bincount(nz[:, 0], minlength=J)
-        buf('jreg_off', i32(torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))))
-        buf('jreg_col', i32(nz[:, 1]))
-        buf('jreg_val', J_regressor[nz[:, 0], nz[:, 1]].contiguous())
-        nzt = torch.nonzero(J_regressor.t(), as_tuple=False)                         # ascending (vertex, joint)
-        counts = torch.bincount(nzt[:, 0], minlength=V)
-        buf('jregT_off', i32(torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))))
-        buf('jregT_row', i32(nzt[:, 1]))
-        buf('jregT_val', J_regressor[nzt[:, 1], nzt[:, 0]].contiguous())
-        buf('weights', lbs_weights.contiguous().clone())
-        buf('rot_pose', rot_pose.contiguous().clone())
-        buf('rot_inverse', rot_inverse.contiguous().clone())
-        buf('rot_identity', torch.eye(3, dtype=torch.float32, device=v_template.device).expand(J, 3, 3).contiguous())
-        self._desc = None
+        own = (('pose_offsets', None if pose_offsets is None else pose_offsets.contiguous().clone()),)
+        self._register_tables(v_template, face_offset, shape_dirs, own, J_regressor, lbs_weights)
+        eye = torch.eye(3, dtype=torch.float32, device=v_template.device)
+        for name, x in (('rot_pose', rot_pose.clone()), ('rot_inverse', rot_inverse.clone()), ('rot_identity', eye)):
+            self.register_buffer(name, x.expand(J, 3, 3).contiguous(), persistent=False)
 
     @classmethod
     def from_layer(cls, smplx_layer, faces, pose, *, face_offset=None, subdivide_num=2, root_joint_idx=0):
@@ -302,41 +348,32 @@ class BodyTemplate(nn.Module):
         directions are ``cat(shapedirs, expr_dirs)``: hand over ``cat(shape_param, zeros)`` as ``coef``, or slice the
         directions yourself and use the constructor.  The three pose constants come from ``pose_constants``."""
         what = 'BodyTemplate.from_layer'
-        f32 = lambda x: x.detach().to(torch.float32)      # noqa: E731
-        v_template = f32(smplx_layer.v_template)
+        v_template, shape_dirs, parents = cls._layer_tables(smplx_layer)
         dev = v_template.device
-        dirs = [f32(smplx_layer.shapedirs)]
-        if getattr(smplx_layer, 'expr_dirs', None) is not None:
-            dirs.append(f32(smplx_layer.expr_dirs))
         check_tensor(what, 'pose', pose, f32=False)
         J = smplx_layer.J_regressor.shape[0]
         if tuple(pose.shape) != (J, 3):
             raise ValueError('%s: pose must be [J, 3] with J = %d (it is %s)' % (what, J, tuple(pose.shape)))
         rot_pose, pose_offsets, rot_inverse = pose_constants(pose, smplx_layer.posedirs)
-        parents = smplx_layer.parents
-        parents = parents.tolist() if isinstance(parents, torch.Tensor) else list(parents)
         up = MeshUpsampler(faces, subdivide_num, num_verts=v_template.shape[0]).to(dev)
-        return cls(v_template, torch.cat(dirs, 2), f32(smplx_layer.J_regressor), f32(smplx_layer.lbs_weights), parents, up,
+        return cls(v_template, shape_dirs, _f32(smplx_layer.J_regressor), _f32(smplx_layer.lbs_weights), parents, up,
                    rot_pose=rot_pose.to(dev), rot_inverse=rot_inverse.to(dev), pose_offsets=pose_offsets.to(dev),
-                   face_offset=None if face_offset is None else f32(face_offset).to(dev), root_joint_idx=root_joint_idx)
+                   face_offset=None if face_offset is None else _f32(face_offset).to(dev), root_joint_idx=root_joint_idx)
 
     def _descriptor(self):
         """(the ``ExaMeshBody`` the C ABI takes, forward workspace bytes, backward workspace bytes); rebuilt when the
         buffers moved."""
-        key = (self.v_base.data_ptr(), self.upsampler._par.data_ptr())
-        if self._desc is None or self._desc[0] != key:
-            p = lambda t: None if t is None else (t.data_ptr() or None)      # noqa: E731
-            up = self.upsampler._plan()
-            d = _lib.ExaMeshBody(self.num_verts, self.num_coef, self.num_joints, self.nnz, self.root_joint_idx,
-                                 ctypes.cast(self._parents, _IP), p(self.v_base), p(self.dirs), p(self.pose_offsets),
-                                 p(self.jreg_off), p(self.jreg_col), p(self.jreg_val), p(self.jregT_off),
-                                 p(self.jregT_row), p(self.jregT_val), p(self.weights), p(self.rot_pose),
-                                 p(self.rot_inverse), p(self.rot_identity),
-                                 ctypes.pointer(self.upsampler._struct[1]))
-            fwd, bwd = ctypes.c_uint64(), ctypes.c_uint64()
-            _lib.MESH.check(_lib.load().exa_mesh_body_workspace_sizes(ctypes.byref(d), ctypes.byref(fwd), ctypes.byref(bwd)))
-            self._desc = (key, d, int(fwd.value), int(bwd.value), up)
-        return ctypes.byref(self._desc[1]), self._desc[2], self._desc[3]
+        def make(p):
+            self.upsampler._plan()      # its struct, which the pointer field below keeps alive
+            return _lib.ExaMeshBody(self.num_verts, self.num_coef, self.num_joints, self.nnz, self.root_joint_idx,
+                                    ctypes.cast(self._parents, _IP), p(self.v_base), p(self.dirs), p(self.pose_offsets),
+                                    p(self.jreg_off), p(self.jreg_col), p(self.jreg_val), p(self.jregT_off),
+                                    p(self.jregT_row), p(self.jregT_val), p(self.weights), p(self.rot_pose),
+                                    p(self.rot_inverse), p(self.rot_identity),
+                                    ctypes.pointer(self.upsampler._struct[1]))
+
+        return self._cached_descriptor((self.v_base.data_ptr(), self.upsampler._par.data_ptr()),
+                                       'exa_mesh_body_workspace_sizes', make)
 
     def forward(self, coef, joint_offset):
         """``coef`` [L] or [1, L] and ``joint_offset`` [J, 3] or [1, J, 3] (float32, ROCm) -> ``BodyOutput``:

@@ -22,6 +22,7 @@
 
 #include "../../include/exa_mesh.h"
 #include "abi_status.h"
+#include "fixed_sum.h"
 
 namespace exa_mesh_impl {
 
@@ -164,9 +165,8 @@ __global__ __launch_bounds__(BLB_BLOCK) void blend_bwd_partial(BlendBwdParams P)
 #pragma unroll
         for (int i = 0; i < BLB_FLIGHT; ++i) {
             float q = ((t[i].x * g[0] + t[i].y * g[1]) + t[i].z * g[2]) + t[i].w * g[3];
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) q = q + __shfl_down(q, off, 64);      // lane 0: the header's tree
-            if (lane == 0) wl[r + i][wave] = q;
+            exa::wave_sum_lane0(q);
+            if (lane == 0) wl[r + i][wave] = q;                                // lane 0: the header's tree
         }
     }
     __syncthreads();

@@ -28,6 +28,7 @@
 #include "../../include/exa_skin.h"
 #include "abi_status.h"
 #include "body.h"
+#include "fixed_sum.h"
 
 namespace exa_mesh_impl {
 
@@ -242,10 +243,7 @@ __global__ __launch_bounds__(64) void body_jreg(JregParams P) {
         }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) p[c] = p[c] + __shfl_down(p[c], off, 64);     // lane 0: the header's tree
-    }
+    for (int c = 0; c < 3; ++c) exa::wave_sum_lane0(p[c]);      // lane 0: the header's tree
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) P.Jr[3 * j + c] = (j == P.root || !P.joint_offset) ? p[c] : p[c] + P.joint_offset[3 * j + c];
@@ -295,8 +293,7 @@ __global__ __launch_bounds__(BD_BLOCK) void body_coef_partial(CoefParams P) {
         const int l = r0 + r;
         const float t = (inside && l < P.L) ? P.dirs[l * ld + m] : 0.0f;
         float q = inside ? t * g : 0.0f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) q = q + __shfl_down(q, off, 64);
+        exa::wave_sum_lane0(q);
         if (lane == 0) wl[r][wave] = q;
     }
     __syncthreads();

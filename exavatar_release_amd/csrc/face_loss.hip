@@ -10,6 +10,7 @@
 // by pixel.  Workgroups are BLOCK = 256 threads (4 waves) on a one-dimensional grid over (image, row, run).
 // No atomics; LDS only for the four wave sums of a workgroup sum.
 #include "common.h"
+#include "fixed_sum.h"
 #include "image_checks.h"
 
 namespace exa {
@@ -37,18 +38,6 @@ __device__ __forceinline__ void store_run(float* p, int x, bool full, int lo, in
         for (int k = 0; k < FACE_RUN; ++k)
             if (x + k >= lo && x + k < hi) p[x + k] = v[k];
     }
-}
-
-// The workgroup sum of include/exa_raster.h: inside a wave a butterfly over lane distances 32, 16, 8, 4, 2, 1
-// (s = s + s[lane ^ distance]: both partners form the same sum, so every lane ends with the wave's), then
-// ((wave 0 + wave 1) + wave 2) + wave 3.  Every thread of the workgroup calls it.
-__device__ __forceinline__ float block_sum(float s) {
-    __shared__ float wave_sum[BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
 }
 
 struct FaceL1Args {
@@ -94,7 +83,7 @@ __global__ __launch_bounds__(BLOCK) void face_l1_fwd_kernel(FaceL1Args a) {
         }
     }
     if (a.partials) {                                        // (uniform: every thread of the workgroup gets here)
-        s = block_sum(s);
+        s = block_sum<BLOCK / 64>(s);
         if (threadIdx.x == 0) a.partials[blockIdx.x] = s;
     }
 }
@@ -102,9 +91,7 @@ __global__ __launch_bounds__(BLOCK) void face_l1_fwd_kernel(FaceL1Args a) {
 // One workgroup: thread t adds partials t, t + 256, t + 512, .. in that order, then the workgroup sum.
 __global__ __launch_bounds__(BLOCK) void face_l1_reduce_kernel(long long n_partials, float n, const float* partials,
                                                                float* out) {
-    float s = 0.0f;
-    for (long long j = threadIdx.x; j < n_partials; j += BLOCK) s = s + partials[j];
-    s = block_sum(s);
+    const float s = block_sum<BLOCK / 64>(strided_sum<BLOCK>(partials, n_partials));
     if (threadIdx.x == 0) *out = s / n;
 }
 

@@ -20,6 +20,7 @@
 //                     the crop come from this kernel.
 //   lpips_normalize / lpips_head_fwd / lpips_head_reduce / lpips_head_bwd   the head, one thread per tap pixel.
 #include "common.h"
+#include "fixed_sum.h"
 #include "image_checks.h"
 
 namespace exa {
@@ -316,15 +317,6 @@ __device__ __forceinline__ float sum_sq(const float* f, int C) {
     return (s0 + s1) + (s2 + s3);
 }
 
-__device__ __forceinline__ float block_sum(float s) {      // as face_loss.hip: butterfly 32 .. 1, then ((w0 + w1) + w2) + w3
-    __shared__ float wave_sum[BLOCK / 64];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-}
-
 __global__ __launch_bounds__(BLOCK) void lpips_normalize(size_t N, int C, const float* f, float* out) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= N) return;
@@ -353,7 +345,7 @@ __global__ __launch_bounds__(BLOCK) void lpips_head_fwd(int npix, int C, const f
         d = (s0 + s1) + (s2 + s3);
         if (dmap) dmap[(size_t)b * npix + i] = d;
     }
-    d = block_sum(d);
+    d = block_sum<BLOCK / 64>(d);
     if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
 }
 
@@ -371,10 +363,9 @@ __global__ __launch_bounds__(BLOCK) void lpips_head_reduce(ReduceArgs a) {
     const int b = blockIdx.x;
     float total = 0.f;
     for (int l = 0; l < a.n_taps; ++l) {
-        float s = 0.f;
-        for (int k = threadIdx.x; k < a.nblk[l]; k += BLOCK) s = s + a.partials[l][(size_t)b * a.nblk[l] + k];
+        float s = strided_sum<BLOCK>(a.partials[l] + (size_t)b * a.nblk[l], a.nblk[l]);
         __syncthreads();                                   // (block_sum's LDS is reused per tap)
-        s = block_sum(s);
+        s = block_sum<BLOCK / 64>(s);
         const float D = s / a.npix[l];
         total = l == 0 ? D : total + D;
     }

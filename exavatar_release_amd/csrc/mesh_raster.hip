@@ -32,6 +32,7 @@
 
 #include "../../include/exa_mesh.h"
 #include "abi_status.h"
+#include "fixed_sum.h"
 
 namespace exa_mesh_impl {
 
@@ -507,8 +508,7 @@ __global__ void __launch_bounds__(BLOCK) mesh_bwd_faces(Params P) {
             acc[3 * k + 2] += dz[k];
         }
     }
-    for (int off = 32; off > 0; off >>= 1)
-        for (int k = 0; k < 9; ++k) acc[k] += __shfl_xor(acc[k], off);
+    for (int k = 0; k < 9; ++k) exa::wave_sum_all(acc[k]);
     if (lane != 0) return;
     float* out = P.grad + gw * 9;
     if (area == 0) {

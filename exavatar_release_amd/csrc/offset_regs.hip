@@ -4,7 +4,7 @@
 //
 //   offset_vertex_fwd   one thread per row (b, v) of the B V rows, OFF_BLOCK = 256 rows per workgroup: the three
 //                       elements of the row for both vertex terms.  Map mode writes them; mean mode adds the row up,
-//                       (t0 + t1) + t2, and the workgroup writes one partial per term (block_sum2, the house sum).
+//                       (t0 + t1) + t2, and the workgroup writes one partial per term (block_sums, the house sum).
 //   offset_joint_fwd    ONE workgroup.  Thread j takes joint elements j, j + 256, .. and pairs j, j + 256, ..; map mode
 //                       writes them, mean mode also adds the vertex partials j, j + 256, .. and writes the four means.
 //   offset_bwd          workgroups 0 .. blocks - 1: one thread per row, every requested vertex gradient; the last
@@ -20,6 +20,7 @@
 
 #include "../../include/exa_mesh.h"
 #include "abi_status.h"
+#include "fixed_sum.h"
 
 namespace exa_mesh_impl {
 
@@ -32,28 +33,10 @@ namespace {
 constexpr int OFF_BLOCK = EXA_MESH_OFFSET_ROWS;
 constexpr int64_t OFF_MAX_ELEMS = 1 << 30;    // B * V * 3
 constexpr int32_t OFF_MAX_JOINTS = 1 << 20;
-static_assert(OFF_BLOCK == 256, "block_sum adds four waves");
 
 __device__ __forceinline__ float off_qnan() { return __int_as_float(0x7fc00000); }
 
 __device__ __forceinline__ float off_sign(float x) { return (x > 0.0f ? 1.0f : 0.0f) - (x < 0.0f ? 1.0f : 0.0f); }
-
-// The workgroup sum of the header, for N values at once: inside a wave a butterfly over lane distances 32, 16, 8, 4, 2, 1
-// (s = s + s[lane ^ distance]: both partners form the same sum, so every lane ends with the wave's), then
-// ((wave 0 + wave 1) + wave 2) + wave 3.  Every thread of the workgroup calls it, once per kernel.
-template <int N>
-__device__ __forceinline__ void block_sums(float (&s)[N]) {
-    __shared__ float wave_sum[N][OFF_BLOCK / 64];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s[k] = s[k] + __shfl_xor(s[k], off);
-        if ((threadIdx.x & 63) == 0) wave_sum[k][threadIdx.x >> 6] = s[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = ((wave_sum[k][0] + wave_sum[k][1]) + wave_sum[k][2]) + wave_sum[k][3];
-}
 
 struct OffsetArgs {
     int32_t V, C, J, n_pairs;                 // C: channels of scale_offset, 1 or 3
@@ -98,7 +81,7 @@ __global__ __launch_bounds__(OFF_BLOCK) void offset_vertex_fwd(OffsetArgs a) {
         s[1] = (ts[0] + ts[1]) + ts[2];
     }
     if (a.partials) {                                          // (uniform: every thread of the workgroup gets here)
-        block_sums(s);
+        exa::block_sums<OFF_BLOCK / 64>(s);      // the header's WG(s)
         if (threadIdx.x == 0) {
             a.partials[blockIdx.x] = s[0];
             a.partials[a.blocks + blockIdx.x] = s[1];
@@ -118,12 +101,7 @@ __device__ __forceinline__ float sym_of(const OffsetArgs& a, int p) {
 __global__ __launch_bounds__(OFF_BLOCK) void offset_joint_fwd(OffsetArgs a) {
     const int tid = threadIdx.x;
     float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (a.means) {
-        for (int64_t j = tid; j < a.blocks; j += OFF_BLOCK) {
-            s[0] = s[0] + a.partials[j];
-            s[1] = s[1] + a.partials[a.blocks + j];
-        }
-    }
+    if (a.means) exa::strided_sums<OFF_BLOCK, 2>(s, a.partials, a.blocks, a.blocks);
     for (int e = tid; e < a.J * 3; e += OFF_BLOCK) {
         const float d = a.jo[e] - a.jref[e];
         const float t = (d * d) * a.w_joint[e];
@@ -136,7 +114,7 @@ __global__ __launch_bounds__(OFF_BLOCK) void offset_joint_fwd(OffsetArgs a) {
         s[3] = s[3] + t;
     }
     if (a.means) {                                             // (uniform)
-        block_sums(s);
+        exa::block_sums<OFF_BLOCK / 64>(s);      // the header's WG(s)
         if (tid < 4) a.means[tid] = s[tid] / a.n[tid];         // N_k == 0: 0 / 0 = NaN, torch.mean of an empty tensor
     }
 }

@@ -13,6 +13,7 @@
 // HBM traffic per Gaussian: reads 1 B per instance + 40 B per BLENDED instance + 32 B of the splat record + 44 B
 // inputs, writes 68 B of gradients (SH: + 12 * M B).
 #include "common.h"
+#include "fixed_sum.h"
 
 namespace exa {
 
@@ -367,8 +368,7 @@ __global__ __launch_bounds__(BLOCK, 2) void preprocess_bwd_kernel(Batch<Preproce
                     }
 #pragma unroll
                     for (int k = 0; k < 10; ++k) {
-#pragma unroll
-                        for (int d = 32; d > 0; d >>= 1) acc[k] += __shfl_xor(acc[k], d, 64);
+                        wave_sum_all(acc[k]);
                         if (lane == L) co[k] = acc[k];
                     }
                 }

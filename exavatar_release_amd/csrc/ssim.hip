@@ -18,6 +18,7 @@
 // conv2d's zero padding) is staged in LDS, filtered horizontally into LDS, then vertically from LDS.  Pure
 // streaming: reads 8 B/pixel, writes 4 (+12 with the derivative maps) B/pixel; backward reads 24, writes 4.
 #include "common.h"
+#include "fixed_sum.h"
 #include "image_checks.h"
 
 namespace exa {
@@ -293,8 +294,8 @@ __global__ __launch_bounds__(PBLOCK2) void photo_stats_kernel(PhotoArgs a, SsimW
         sum_l1 += a.l1w ? d * a.l1w[mplane + g] : d;
     }
     // deterministic block reduction -> one pair of partial sums per workgroup
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { sum_ssim += __shfl_xor(sum_ssim, d, 64); sum_l1 += __shfl_xor(sum_l1, d, 64); }
+    wave_sum_all(sum_ssim);
+    wave_sum_all(sum_l1);
     if ((tid & 63) == 0) { s_red[0][tid >> 6] = sum_ssim; s_red[1][tid >> 6] = sum_l1; }
     __syncthreads();
     if (tid == 0) {

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, check_no_grad, check_tensor, grad_in, launch
+from ._device import _ptr, check_no_grad, check_reduce, check_tensor, grad_in, launch
 from .losses import _c_crop, _crop_window
 
 
@@ -121,8 +121,7 @@ class FaceRGBLoss(nn.Module):
 
     def forward(self, img_out, face_render, img_target, bbox=None, reduce=None):
         what = 'FaceRGBLoss'
-        if reduce not in (None, 'mean'):
-            raise ValueError("%s: reduce must be None or 'mean' (it is %r)" % (what, reduce))
+        check_reduce(what, reduce)
         everything = _check_images(what, [('img_out', img_out), ('img_target', img_target)], 'face_render', face_render)
         check_no_grad(what, 'img_target', img_target)
         _on_one_device(what, everything)

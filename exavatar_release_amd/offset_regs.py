@@ -41,8 +41,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _ptrs, _workspace, check_no_grad, check_tensor, grad_in, launch
-from .vertex_regs import _check_devices, _check_mask, _check_shape
+from ._device import (_ptr, _ptrs, _workspace, check_devices, check_mask, check_no_grad, check_reduce, check_shape,
+                      check_tensor, grad_in, launch)
 
 TERMS = ('gaussian_mean_reg', 'gaussian_scale_reg', 'joint_offset_reg', 'joint_offset_sym_reg')      # model.py's key order
 ROWS = 256                # EXA_MESH_OFFSET_ROWS
@@ -164,11 +164,6 @@ def _weight_rows(what, name, w, V):
     return w.reshape(V).contiguous()
 
 
-def _check_reduce(what, reduce):
-    if reduce not in (None, 'mean'):
-        raise ValueError("%s: reduce must be None or 'mean' (it is %r)" % (what, reduce))
-
-
 def offset_regs(mean_offset, mean_offset_offset, scale, scale_offset, joint_offset, mean_weight, scale_weight,
                 joint_offset_ref, joint_weight, sym_pairs, reduce='mean'):
     """The four terms for a caller's own constants: a dict in ``TERMS`` order (module docstring).  ``mean_weight``,
@@ -176,24 +171,24 @@ def offset_regs(mean_offset, mean_offset_offset, scale, scale_offset, joint_offs
     ``(right, left)`` index lists as ``symmetric_joint_pairs`` returns them (or None), whose device tables are cached per
     pair of lists and device.  Gradients go to whichever of the five inputs require them."""
     what = 'offset_regs'
-    _check_reduce(what, reduce)
-    _check_shape(what, 'mean_offset', mean_offset, (None, None, 3), '[B, V, 3]')
+    check_reduce(what, reduce)
+    check_shape(what, 'mean_offset', mean_offset, (None, None, 3), '[B, V, 3]')
     B, V = mean_offset.shape[:2]
     like = '[%d, %d, 3], the shape of mean_offset' % (B, V)
-    _check_shape(what, 'mean_offset_offset', mean_offset_offset, (B, V, 3), like)
-    _check_shape(what, 'scale', scale, (B, V, 3), like)
+    check_shape(what, 'mean_offset_offset', mean_offset_offset, (B, V, 3), like)
+    check_shape(what, 'scale', scale, (B, V, 3), like)
     check_tensor(what, 'scale_offset', scale_offset)
     if scale_offset.dim() != 3 or tuple(scale_offset.shape[:2]) != (B, V) or scale_offset.shape[2] not in (1, 3):
         raise ValueError('%s: scale_offset must be [%d, %d, 1] or [%d, %d, 3] (it is %s)'
                          % (what, B, V, B, V, tuple(scale_offset.shape)))
-    _check_shape(what, 'joint_offset', joint_offset, (None, 3), '[J, 3]')
+    check_shape(what, 'joint_offset', joint_offset, (None, 3), '[J, 3]')
     J = joint_offset.shape[0]
     w_mean = _weight_rows(what, 'mean_weight', mean_weight, V)
     w_scale = _weight_rows(what, 'scale_weight', scale_weight, V)
     for name, x in (('joint_offset_ref', joint_offset_ref), ('joint_weight', joint_weight)):
-        _check_shape(what, name, x, (J, 3), '[J, 3] with J = %d' % J)
+        check_shape(what, name, x, (J, 3), '[J, 3] with J = %d' % J)
         check_no_grad(what, name, x)
-    _check_devices(what, 'joint_offset', joint_offset, mean_offset=mean_offset, mean_offset_offset=mean_offset_offset,
+    check_devices(what, 'joint_offset', joint_offset, mean_offset=mean_offset, mean_offset_offset=mean_offset_offset,
                    scale=scale, scale_offset=scale_offset, mean_weight=mean_weight, scale_weight=scale_weight,
                    joint_offset_ref=joint_offset_ref, joint_weight=joint_weight)
     pair_r, pair_l, joint_pair = _device_pairs(sym_pairs, J, joint_offset.device, what)
@@ -219,9 +214,9 @@ class OffsetRegs(nn.Module):
         V = mean_weight.numel()
         w_mean = _weight_rows(what, 'mean_weight', mean_weight, V)
         w_scale = _weight_rows(what, 'scale_weight', scale_weight, V)
-        _check_shape(what, 'joint_offset_ref', joint_offset_ref, (None, 3), '[J, 3]')
+        check_shape(what, 'joint_offset_ref', joint_offset_ref, (None, 3), '[J, 3]')
         J = joint_offset_ref.shape[0]
-        _check_shape(what, 'joint_weight', joint_weight, (J, 3), '[J, 3] with J = %d' % J)
+        check_shape(what, 'joint_weight', joint_weight, (J, 3), '[J, 3] with J = %d' % J)
         for name, x in (('joint_offset_ref', joint_offset_ref), ('joint_weight', joint_weight)):
             check_no_grad(what, name, x)
         dev = joint_offset_ref.device
@@ -256,8 +251,8 @@ class JointOffsetSymmetricReg(nn.Module):
 
     def forward(self, joint_offset):
         what = 'JointOffsetSymmetricReg'
-        _check_shape(what, 'joint_offset', joint_offset, (self.joint_num, 3), '[J, 3] with J = %d' % self.joint_num)
-        _check_devices(what, 'joint_offset', joint_offset)
+        check_shape(what, 'joint_offset', joint_offset, (self.joint_num, 3), '[J, 3] with J = %d' % self.joint_num)
+        check_devices(what, 'joint_offset', joint_offset)
         dev = joint_offset.device
         if self.joint_pair.device != dev:                        # a module that was never moved: the tables follow the input
             for name in ('pair_right', 'pair_left', 'joint_pair'):
@@ -282,7 +277,7 @@ def loss_weights(is_rhand, is_lhand, is_face, is_face_expr, is_cavity, joint_par
         raise ValueError('%s: is_rhand must be a bool [V] tensor' % what)
     V, dev = is_rhand.shape[0], is_rhand.device
     for name, m in masks:
-        _check_mask(what, name, m, V)
+        check_mask(what, name, m, V)
         if m.device != dev:
             raise ValueError('%s: %s is not on the device of is_rhand' % (what, name))
     r, l, f, fe, cav = (m for _, m in masks)

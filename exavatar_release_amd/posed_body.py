@@ -31,13 +31,10 @@ import collections
 import ctypes
 
 import torch
-import torch.nn as nn
 
 from . import _lib
 from ._device import _ptr, _workspace, check_no_grad, check_tensor, config, grad_in, launch
-from .kinematics import MAX_JOINTS, _tree
-
-MAX_COEF = 512           # EXA_MESH_BODY_MAX_COEF
+from .body import _f32, _SmplxTables
 
 PosedBodyOutput = collections.namedtuple('PosedBodyOutput', ['vertices', 'joints', 'vertices_world', 'rot'])
 
@@ -90,7 +87,7 @@ class _Posed(torch.autograd.Function):
         return dpose, dbetas, dexpr, dtransl, djo, None, None, None
 
 
-class PosedBody(nn.Module):
+class PosedBody(_SmplxTables):
     """The posed SMPL-X layer of ``get_smplx_outputs`` (module docstring).
 
     ``v_template`` [V, 3], ``shape_dirs`` [V, 3, L] (1 <= L <= 512: ``cat(shapedirs, expr_dirs)``), ``posedirs``
@@ -104,32 +101,11 @@ class PosedBody(nn.Module):
                  face_offset=None):
         super(PosedBody, self).__init__()
         what = 'PosedBody'
-        named = (('v_template', v_template), ('shape_dirs', shape_dirs), ('posedirs', posedirs),
-                 ('J_regressor', J_regressor), ('lbs_weights', lbs_weights), ('pose_mean', pose_mean),
-                 ('face_offset', face_offset))
-        for name, x in named:
-            if x is None and name in ('pose_mean', 'face_offset'):
-                continue
-            check_tensor(what, name, x)
-            check_no_grad(what, name, x)
-            if x.device != v_template.device:
-                raise ValueError('%s: %s is not on the device of v_template' % (what, name))
-        if v_template.dim() != 2 or v_template.shape[1] != 3 or v_template.shape[0] < 1:
-            raise ValueError('%s: v_template must be [V, 3] (it is %s)' % (what, tuple(v_template.shape)))
-        V = v_template.shape[0]
-        if shape_dirs.dim() != 3 or tuple(shape_dirs.shape[:2]) != (V, 3) or not 1 <= shape_dirs.shape[2] <= MAX_COEF:
-            raise ValueError('%s: shape_dirs must be [V, 3, L] with V = %d and 1 <= L <= %d (it is %s)'
-                             % (what, V, MAX_COEF, tuple(shape_dirs.shape)))
-        L = shape_dirs.shape[2]
-        if J_regressor.dim() != 2 or J_regressor.shape[1] != V or not 1 <= J_regressor.shape[0] <= MAX_JOINTS:
-            raise ValueError('%s: J_regressor must be [J, V] with V = %d and 1 <= J <= %d (it is %s)'
-                             % (what, V, MAX_JOINTS, tuple(J_regressor.shape)))
-        J = J_regressor.shape[0]
-        self._parents = _tree(what, parents)
-        if len(self._parents) != J:
-            raise ValueError('%s: parents names %d joints, J_regressor %d' % (what, len(self._parents), J))
-        if tuple(lbs_weights.shape) != (V, J):
-            raise ValueError('%s: lbs_weights must be [V, J] = [%d, %d] (it is %s)' % (what, V, J, tuple(lbs_weights.shape)))
+        self._check_data(what, (('v_template', v_template, False), ('shape_dirs', shape_dirs, False),
+                                ('posedirs', posedirs, False), ('J_regressor', J_regressor, False),
+                                ('lbs_weights', lbs_weights, False), ('pose_mean', pose_mean, True),
+                                ('face_offset', face_offset, True)))
+        V, _, J = self._check_tables(what, v_template, shape_dirs, J_regressor, parents, lbs_weights)
         if tuple(posedirs.shape) != (9 * (J - 1), 3 * V):
             raise ValueError('%s: posedirs must be [9 (J - 1), 3 V] = [%d, %d] (it is %s)'
                              % (what, 9 * (J - 1), 3 * V, tuple(posedirs.shape)))
@@ -137,61 +113,34 @@ class PosedBody(nn.Module):
             raise ValueError('%s: pose_mean must hold 3 J = %d values (it is %s)' % (what, 3 * J, tuple(pose_mean.shape)))
         if face_offset is not None and tuple(face_offset.shape) != (V, 3):
             raise ValueError('%s: face_offset must be [V, 3] with V = %d (it is %s)' % (what, V, tuple(face_offset.shape)))
-        self.num_verts, self.num_coef, self.num_joints = V, L, J
-        i32 = lambda x: x.to(torch.int32).contiguous()      # noqa: E731
-        buf = lambda name, x: self.register_buffer(name, x, persistent=False)      # noqa: E731
-        buf('v_base', (v_template if face_offset is None else v_template + face_offset).contiguous().clone())
-        buf('dirs', shape_dirs.reshape(3 * V, L).t().contiguous())                   # feature-major [L, 3 V]
-        buf('posedirs', posedirs.contiguous().clone())
-        buf('pose_mean', None if pose_mean is None else pose_mean.reshape(J, 3).contiguous().clone())
-        nz = torch.nonzero(J_regressor, as_tuple=False)                              # ascending (joint, vertex)
-        self.nnz = int(nz.shape[0])
-        counts = torch.bincount(nz[:, 0], minlength=J)
-        buf('jreg_off', i32(torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))))
-        buf('jreg_col', i32(nz[:, 1]))
-        buf('jreg_val', J_regressor[nz[:, 0], nz[:, 1]].contiguous())
-        nzt = torch.nonzero(J_regressor.t(), as_tuple=False)                         # ascending (vertex, joint)
-        counts = torch.bincount(nzt[:, 0], minlength=V)
-        buf('jregT_off', i32(torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))))
-        buf('jregT_row', i32(nzt[:, 1]))
-        buf('jregT_val', J_regressor[nzt[:, 1], nzt[:, 0]].contiguous())
-        buf('weights', lbs_weights.contiguous().clone())
-        self._desc = None
-        self.debug_workspace = None           # config.keep_debug: the most recent forward's workspace
+        own = (('posedirs', posedirs.contiguous().clone()),
+               ('pose_mean', None if pose_mean is None else pose_mean.reshape(J, 3).contiguous().clone()))
+        self._register_tables(v_template, face_offset, shape_dirs, own, J_regressor, lbs_weights)
+        self.debug_workspace = None          # config.keep_debug: the most recent forward's workspace
 
     @classmethod
     def from_layer(cls, smplx_layer, *, face_offset=None):
         """From a (vendored) smplx ``SMPLX`` layer: its ``v_template``, ``cat(shapedirs, expr_dirs)``, ``posedirs``,
         ``J_regressor``, ``lbs_weights``, ``parents`` and ``pose_mean`` (a layer without one, or with ``flat_hand_mean``'s
         zeros, adds nothing that changes a value)."""
-        f32 = lambda x: x.detach().to(torch.float32)      # noqa: E731
-        v_template = f32(smplx_layer.v_template)
+        v_template, shape_dirs, parents = cls._layer_tables(smplx_layer)
         dev = v_template.device
-        dirs = [f32(smplx_layer.shapedirs)]
-        if getattr(smplx_layer, 'expr_dirs', None) is not None:
-            dirs.append(f32(smplx_layer.expr_dirs))
-        parents = smplx_layer.parents
-        parents = parents.tolist() if isinstance(parents, torch.Tensor) else list(parents)
         pose_mean = getattr(smplx_layer, 'pose_mean', None)
-        return cls(v_template, torch.cat(dirs, 2), f32(smplx_layer.posedirs), f32(smplx_layer.J_regressor),
-                   f32(smplx_layer.lbs_weights), parents,
-                   pose_mean=None if pose_mean is None else f32(torch.as_tensor(pose_mean)).to(dev),
-                   face_offset=None if face_offset is None else f32(face_offset).to(dev))
+        return cls(v_template, shape_dirs, _f32(smplx_layer.posedirs), _f32(smplx_layer.J_regressor),
+                   _f32(smplx_layer.lbs_weights), parents,
+                   pose_mean=None if pose_mean is None else _f32(torch.as_tensor(pose_mean)).to(dev),
+                   face_offset=None if face_offset is None else _f32(face_offset).to(dev))
 
     def _descriptor(self):
         """(the ``ExaMeshPosed`` the C ABI takes, forward workspace bytes, backward workspace bytes); rebuilt when the
         buffers moved."""
-        key = self.v_base.data_ptr()
-        if self._desc is None or self._desc[0] != key:
-            p = lambda t: None if t is None else (t.data_ptr() or None)      # noqa: E731
-            d = _lib.ExaMeshPosed(self.num_verts, self.num_coef, self.num_joints, self.nnz,
-                                  ctypes.cast(self._parents, _IP), p(self.v_base), p(self.dirs), p(self.posedirs),
-                                  p(self.pose_mean), p(self.jreg_off), p(self.jreg_col), p(self.jreg_val),
-                                  p(self.jregT_off), p(self.jregT_row), p(self.jregT_val), p(self.weights))
-            fwd, bwd = ctypes.c_uint64(), ctypes.c_uint64()
-            _lib.MESH.check(_lib.load().exa_mesh_posed_workspace_sizes(ctypes.byref(d), ctypes.byref(fwd), ctypes.byref(bwd)))
-            self._desc = (key, d, int(fwd.value), int(bwd.value))
-        return ctypes.byref(self._desc[1]), self._desc[2], self._desc[3]
+        def make(p):
+            return _lib.ExaMeshPosed(self.num_verts, self.num_coef, self.num_joints, self.nnz,
+                                     ctypes.cast(self._parents, _IP), p(self.v_base), p(self.dirs), p(self.posedirs),
+                                     p(self.pose_mean), p(self.jreg_off), p(self.jreg_col), p(self.jreg_val),
+                                     p(self.jregT_off), p(self.jregT_row), p(self.jregT_val), p(self.weights))
+
+        return self._cached_descriptor(self.v_base.data_ptr(), 'exa_mesh_posed_workspace_sizes', make)
 
     def forward(self, pose, betas, expression, transl, joint_offset=None, R=None, t=None):
         """``pose`` [J, 3] axis-angle in the layer's joint order, ``betas`` [Lb], ``expression`` [Le] (Lb + Le == L, either

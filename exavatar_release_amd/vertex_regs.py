@@ -55,7 +55,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _workspace, check_no_grad, check_tensor, grad_in, launch
+from ._device import (_ptr, _workspace, check_devices, check_mask, check_no_grad, check_shape, check_tensor, grad_in,
+                      launch)
 
 MAX_TOP_K = 64            # EXA_MESH_ARM_MAX_K
 ARM_WAVES = 8             # EXA_MESH_ARM_WAVES
@@ -65,27 +66,6 @@ CHUNK = 256               # EXA_MESH_REG_CHUNK
 
 
 # ---- argument checks: dtype and shape first, the device last, each a ValueError naming the argument -------------------
-def _check_shape(what, name, x, shape, text):
-    check_tensor(what, name, x)
-    if x.dim() != len(shape) or any(s is not None and x.shape[i] != s for i, s in enumerate(shape)):
-        raise ValueError('%s: %s must be %s (it is %s)' % (what, name, text, tuple(x.shape)))
-
-
-def _check_mask(what, name, m, V):
-    if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or m.dim() != 1 or m.shape[0] != V:
-        raise ValueError('%s: %s must be a bool [V] tensor with V = %d (it is %s)' % (
-            what, name, V, '%s %s' % (m.dtype, tuple(m.shape)) if isinstance(m, torch.Tensor) else type(m).__name__))
-
-
-def _check_devices(what, anchor_name, anchor, **others):
-    if anchor.device.type != 'cuda':
-        raise ValueError('%s: %s must be on a ROCm device (it is on %s; there is no CPU path)'
-                         % (what, anchor_name, anchor.device))
-    for name, x in others.items():
-        if x is not None and x.device != anchor.device:
-            raise ValueError('%s: %s is not on the device of %s' % (what, name, anchor_name))
-
-
 def _normal_rows(what, normal, V):
     check_tensor(what, 'normal', normal)
     check_no_grad(what, 'normal', normal)
@@ -151,10 +131,10 @@ def arm_neighbors(mesh_neutral_pose, is_upper_arm, is_lower_arm, dist_x_thr=0.01
     bound on the number of lower-arm vertices (default V, always safe): it sizes the selection's grid and lists, since
     the true L stays on the device; lower-arm vertices beyond it get NaN.  Three launches, no synchronisation."""
     what = 'arm_neighbors'
-    _check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
+    check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
     V = mesh_neutral_pose.shape[0]
-    _check_mask(what, 'is_upper_arm', is_upper_arm, V)
-    _check_mask(what, 'is_lower_arm', is_lower_arm, V)
+    check_mask(what, 'is_upper_arm', is_upper_arm, V)
+    check_mask(what, 'is_lower_arm', is_lower_arm, V)
     if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= MAX_TOP_K:
         raise ValueError('%s: top_k must be an integer 1 .. %d (it is %r)' % (what, MAX_TOP_K, top_k))
     thr = float(dist_x_thr)
@@ -166,7 +146,7 @@ def arm_neighbors(mesh_neutral_pose, is_upper_arm, is_lower_arm, dist_x_thr=0.01
     rows = V if row_capacity is None else int(row_capacity)
     if not 0 <= rows <= V:
         raise ValueError('%s: row_capacity must be 0 .. V = %d (it is %r)' % (what, V, row_capacity))
-    _check_devices(what, 'mesh_neutral_pose', mesh_neutral_pose, is_upper_arm=is_upper_arm, is_lower_arm=is_lower_arm)
+    check_devices(what, 'mesh_neutral_pose', mesh_neutral_pose, is_upper_arm=is_upper_arm, is_lower_arm=is_lower_arm)
     mesh = mesh_neutral_pose.detach().contiguous()
     up, lo = is_upper_arm.contiguous(), is_lower_arm.contiguous()
     plan = ArmPlan(V, rows, top_k, thr32, mesh.device)
@@ -211,7 +191,7 @@ def arm_rgb_loss(plan, rgb, return_d=False):
     what = 'arm_rgb_loss'
     if not isinstance(plan, ArmPlan):
         raise ValueError('%s: plan must be an ArmPlan (arm_neighbors)' % what)
-    _check_shape(what, 'rgb', rgb, (None, plan.V, 3), '[B, V, 3] with V = %d' % plan.V)
+    check_shape(what, 'rgb', rgb, (None, plan.V, 3), '[B, V, 3] with V = %d' % plan.V)
     if rgb.device != plan.device:
         raise ValueError('%s: rgb is not on the device of plan' % what)
     loss, d = _ArmLoss.apply(rgb.contiguous(), plan)
@@ -251,16 +231,16 @@ def get_arm(mesh_neutral_pose, skinning_weight, face, arm_joint_idx, normal=None
     double ``math.cos(math.pi / 3) = 0.5000000000000001``; no float32 lies between 0.5 and that, so ``> 0.5f`` and
     ``<= 0.5f`` decide identically."""
     what = 'get_arm'
-    _check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
+    check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
     V = mesh_neutral_pose.shape[0]
-    _check_shape(what, 'skinning_weight', skinning_weight, (V, None), '[V, J] with V = %d' % V)
+    check_shape(what, 'skinning_weight', skinning_weight, (V, None), '[V, J] with V = %d' % V)
     check_no_grad(what, 'skinning_weight', skinning_weight, 'a buffer')
     joints = [int(j) for j in arm_joint_idx]
     if not joints or any(not 0 <= j < skinning_weight.shape[1] for j in joints):
         raise ValueError('%s: arm_joint_idx must name joints in [0, %d)' % (what, skinning_weight.shape[1]))
     if normal is not None:
         normal = _normal_rows(what, normal, V)
-    _check_devices(what, 'mesh_neutral_pose', mesh_neutral_pose, skinning_weight=skinning_weight, normal=normal)
+    check_devices(what, 'mesh_neutral_pose', mesh_neutral_pose, skinning_weight=skinning_weight, normal=normal)
     if normal is None:
         normal = _normals_of(mesh_neutral_pose, face)
     part_label = skinning_weight.argmax(1)
@@ -332,16 +312,16 @@ class HandRGBReg(nn.Module):
 
     def forward(self, rgb, is_rhand, is_lhand):
         what = 'HandRGBReg'
-        _check_shape(what, 'rgb', rgb, (None, None, 3), '[B, V, 3]')
+        check_shape(what, 'rgb', rgb, (None, None, 3), '[B, V, 3]')
         V = rgb.shape[1]
-        _check_mask(what, 'is_rhand', is_rhand, V)
-        _check_mask(what, 'is_lhand', is_lhand, V)
+        check_mask(what, 'is_rhand', is_rhand, V)
+        check_mask(what, 'is_lhand', is_lhand, V)
         tables = _hands(is_rhand, is_lhand)
         (r_idx, r_rank), (l_idx, l_rank) = tables['r'], tables['l']
         if r_idx.shape[0] != l_idx.shape[0]:
             raise ValueError('%s: is_rhand and is_lhand must select equally many vertices (they select %d and %d)'
                              % (what, r_idx.shape[0], l_idx.shape[0]))
-        _check_devices(what, 'rgb', rgb, is_rhand=is_rhand, is_lhand=is_lhand)
+        check_devices(what, 'rgb', rgb, is_rhand=is_rhand, is_lhand=is_lhand)
         return _HandRgb.apply(rgb.contiguous(), r_idx, l_idx, r_rank, l_rank)
 
 
@@ -383,14 +363,14 @@ class HandMeanReg(nn.Module):
 
     def forward(self, mesh_neutral_pose, offset, is_rhand, is_lhand, normal=None):
         what = 'HandMeanReg'
-        _check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
+        check_shape(what, 'mesh_neutral_pose', mesh_neutral_pose, (None, 3), '[V, 3]')
         V = mesh_neutral_pose.shape[0]
-        _check_shape(what, 'offset', offset, (None, V, 3), '[B, V, 3] with V = %d' % V)
-        _check_mask(what, 'is_rhand', is_rhand, V)
-        _check_mask(what, 'is_lhand', is_lhand, V)
+        check_shape(what, 'offset', offset, (None, V, 3), '[B, V, 3] with V = %d' % V)
+        check_mask(what, 'is_rhand', is_rhand, V)
+        check_mask(what, 'is_lhand', is_lhand, V)
         if normal is not None:
             normal = _normal_rows(what, normal, V)
-        _check_devices(what, 'offset', offset, mesh_neutral_pose=mesh_neutral_pose, is_rhand=is_rhand, is_lhand=is_lhand,
+        check_devices(what, 'offset', offset, mesh_neutral_pose=mesh_neutral_pose, is_rhand=is_rhand, is_lhand=is_lhand,
                        normal=normal)
         if normal is None:
             normal = _normals_of(mesh_neutral_pose, self.face)

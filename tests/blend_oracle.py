@@ -31,6 +31,8 @@
 """
 import numpy as np
 
+from tests import sum_oracle
+
 U = 2.0 ** -24
 SEGMENTS = 8         # EXA_MESH_BLEND_SEGMENTS
 CHUNK = 1024         # EXA_MESH_BLEND_CHUNK
@@ -109,11 +111,7 @@ def backward32(table, cols, inv, g_out, g_masked=None):
         for i in (1, 2, 3):
             prod = T[..., i] * g[None, :, :, i]
             q = q + prod
-        q = q.reshape(q.shape[0], chunks, 4, 64)
-        for off in (32, 16, 8, 4, 2, 1):
-            q = q[..., :off] + q[..., off:2 * off]
-        w = q[..., 0]                                      # [rows, chunks, 4 waves]
-        partial = ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+        partial = sum_oracle.waves(sum_oracle.tree(q.reshape(q.shape[0], chunks, 4, 64)))      # [rows, chunks]
         acc = np.zeros(partial.shape[0], dtype=np.float32)
         for c in range(chunks):
             acc = acc + partial[:, c]

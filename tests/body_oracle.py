@@ -15,6 +15,7 @@ import numpy as np
 
 import kin_oracle
 import skin_oracle
+import sum_oracle
 
 U = 2.0 ** -24
 CHUNK = 256      # EXA_MESH_BODY_CHUNK
@@ -83,14 +84,45 @@ def max_dependants(pl):
     return [int(np.bincount(edges.reshape(-1), minlength=1).max()) if edges.size else 0 for _, edges in pl['rounds']]
 
 
+# ---- the sums the stage shares with the posed stage (tests/posed_oracle.py) -------------------------------------------
+def blend(coef, dirs, base, dt):
+    """base [M] + the sum over the rows of dirs [n, M] from +0.0 in ascending row."""
+    s = np.zeros(dirs.shape[1], dtype=dt)
+    for l in range(dirs.shape[0]):
+        s = s + coef[l] * dirs[l]
+    return base + s
+
+
+def regress(reg, reg_dt, vs, dt):
+    """[J, 3]: every row of the regressor over its non-zeros, lanes then the tree."""
+    Jr = np.zeros((reg.shape[0], 3), dtype=dt)
+    for j in range(reg.shape[0]):
+        cols = np.nonzero(reg[j])[0]
+        vals = reg_dt[j, cols]
+        p = np.zeros((64, 3), dtype=dt)
+        for i0 in range(0, cols.size, 64):
+            n = min(64, cols.size - i0)
+            p[:n] = p[:n] + vals[i0:i0 + n, None] * vs[cols[i0:i0 + n]]
+        Jr[j] = sum_oracle.tree(p.T)
+    return Jr
+
+
+def two_level(T, g, dt):
+    """[n]: sum_m T[l][m] g[m] over chunks of 256 (lanes, the tree per wave, the four waves), then the chunks in order."""
+    n, M = T.shape
+    chunks = -(-M // CHUNK)
+    gq = np.zeros(chunks * CHUNK, dtype=dt)
+    gq[:M] = g
+    Tp = np.zeros((n, chunks * CHUNK), dtype=dt)
+    Tp[:, :M] = T
+    partial = sum_oracle.waves(sum_oracle.tree((Tp * gq[None]).reshape(n, chunks, 4, 64)))
+    out = np.zeros(n, dtype=dt)
+    for ch in range(chunks):
+        out = out + partial[:, ch]
+    return out
+
+
 # ---- the stage --------------------------------------------------------------------------------------------------------
-def _tree_sum(p):
-    """The 64 lanes (axis 0) added as the header's tree; returns lane 0."""
-    for off in (32, 16, 8, 4, 2, 1):
-        p = p[:off] + p[off:2 * off]
-    return p[0]
-
-
 def _prepare(case, dt, magnitude):
     f = (lambda a: None if a is None else np.abs(np.asarray(a, dtype=dt))) if magnitude else \
         (lambda a: None if a is None else np.asarray(a, dtype=dt))
@@ -108,22 +140,11 @@ def forward(case, coef, joint_offset, dtype=np.float32, magnitude=False):
     V, L = c['shape_dirs'].shape[0], c['shape_dirs'].shape[2]
     J = c['J_regressor'].shape[0]
     base = c['v_template'] if c['face_offset'] is None else c['v_template'] + c['face_offset']
-    dirs = c['shape_dirs'].reshape(3 * V, L)
-    s = np.zeros(3 * V, dtype=dt)
-    for l in range(L):
-        s = s + coef[l] * dirs[:, l]
-    vs = base + s.reshape(V, 3)
+    vs = blend(coef, c['shape_dirs'].reshape(3 * V, L).T, base.reshape(-1), dt).reshape(V, 3)
     vp = vs if c['pose_offsets'] is None else vs + c['pose_offsets']
-    Jr = np.zeros((J, 3), dtype=dt)
-    reg = np.asarray(case['J_regressor'])
-    for j in range(J):
-        cols = np.nonzero(reg[j])[0]
-        vals = c['J_regressor'][j, cols]
-        p = np.zeros((64, 3), dtype=dt)
-        for i0 in range(0, cols.size, 64):
-            n = min(64, cols.size - i0)
-            p[:n] = p[:n] + vals[i0:i0 + n, None] * vs[cols[i0:i0 + n]]
-        Jr[j] = _tree_sum(p) if j == root else _tree_sum(p) + jo[j]
+    Jr = regress(np.asarray(case['J_regressor']), c['J_regressor'], vs, dt)
+    others = np.arange(J) != root                  # the root's joint gets no offset (not even + 0)
+    Jr[others] = Jr[others] + jo[others]
     A, jnp = kin_oracle.forward(c['rot_pose'][None], Jr[None], parents, None, dt, magnitude)
     mesh = skin_oracle.forward([vp], A[0], c['weights'], None, None, None, None, dt)[0]
     pl = plan(case['faces'], V, case['levels'])
@@ -181,19 +202,7 @@ def backward(case, fwd, cot, dtype=np.float32, magnitude=False, want_coef=True):
     for j in range(J):                  # ascending joint: a vertex meets its column's non-zeros in that order
         cols = np.nonzero(reg[j])[0]
         dvs[cols] = dvs[cols] + c['J_regressor'][j, cols, None] * dJ[j]
-    M = 3 * V
-    chunks = -(-M // CHUNK)
-    gq = np.zeros(chunks * CHUNK, dtype=dt)
-    gq[:M] = dvs.reshape(-1)
-    T = np.zeros((L, chunks * CHUNK), dtype=dt)
-    T[:, :M] = c['shape_dirs'].reshape(M, L).T
-    q = (T * gq[None]).reshape(L, chunks, 4, 64)
-    q = _tree_sum(np.moveaxis(q, 3, 0))                  # [L, chunks, 4 waves]
-    partial = ((q[..., 0] + q[..., 1]) + q[..., 2]) + q[..., 3]
-    dcoef = np.zeros(L, dtype=dt)
-    for ch in range(chunks):
-        dcoef = dcoef + partial[:, ch]
-    return dcoef, djo
+    return two_level(c['shape_dirs'].reshape(3 * V, L).T, dvs.reshape(-1), dt), djo
 
 
 # ---- first-order error bounds: |fp32 - exact| <= K u * magnitude ------------------------------------------------------

@@ -7,7 +7,9 @@ Arrays: ``mo``, ``moo``, ``sc`` [B, V, 3]; ``so`` [B, V, 1] or [B, V, 3]; ``wm``
 (``blocks``, ``mean_depth``) and the small random cases of the tests."""
 import numpy as np
 
-BLOCK = 256               # EXA_MESH_OFFSET_ROWS: rows per workgroup = threads of a workgroup
+from tests import sum_oracle
+
+BLOCK = 256              # EXA_MESH_OFFSET_ROWS: rows per workgroup = threads of a workgroup
 TERMS = ('gaussian_mean_reg', 'gaussian_scale_reg', 'joint_offset_reg', 'joint_offset_sym_reg')
 F32 = np.float32
 
@@ -33,30 +35,6 @@ def maps(mo, moo, sc, so, wm, ws, jo, ref, wj, pr, pl, dtype=F32):
 
 
 # ---- the sums -----------------------------------------------------------------------------------------------------------
-def wg_sum(s):
-    """WG of the header over [..., 256] float32: per wave of 64 lanes the butterfly over lane distances 32 .. 1, then
-    ((wave 0 + wave 1) + wave 2) + wave 3."""
-    s = np.array(s, dtype=F32).reshape(s.shape[:-1] + (4, 64))
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        s = s + s[..., lane ^ off]
-    w = s[..., 0]
-    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
-
-
-def strided_sum(x):
-    """One workgroup over a flat float32 array: thread j adds x[j], x[j + 256], .. in order from +0, then WG."""
-    x = np.asarray(x, dtype=F32).reshape(-1)
-    trips = (x.size + BLOCK - 1) // BLOCK
-    pad = np.zeros(trips * BLOCK, F32)
-    pad[:x.size] = x
-    live = (np.arange(trips * BLOCK) < x.size).reshape(trips, BLOCK)
-    s = np.zeros(BLOCK, F32)
-    for t, row in enumerate(pad.reshape(trips, BLOCK)):
-        s = np.where(live[t], s + row, s)
-    return wg_sum(s)
-
-
 def vertex_partials(vmap):
     """[blocks] float32 of a [B, V, 3] map: per row (t0 + t1) + t2, +0 past the last row, WG per 256 consecutive rows."""
     rows = np.asarray(vmap, dtype=F32).reshape(-1, 3)
@@ -64,13 +42,13 @@ def vertex_partials(vmap):
     n = blocks_of_rows(rows.shape[0])
     pad = np.zeros(n * BLOCK, F32)
     pad[:r.size] = r
-    return wg_sum(pad.reshape(n, BLOCK)) if n else np.zeros(0, F32)
+    return sum_oracle.wg_sum(pad.reshape(n, BLOCK)) if n else np.zeros(0, F32)
 
 
 def means32(all_maps):
-    """[4] float32: the header's means of the four float32 maps; an empty map gives NaN."""
-    sums = [strided_sum(vertex_partials(all_maps[0])), strided_sum(vertex_partials(all_maps[1])),
-            strided_sum(all_maps[2]), strided_sum(all_maps[3])]
+    """[4] float32: the header's means of the four float32 maps (an empty map: NaN); each sum the strided sum, then WG."""
+    flat = [vertex_partials(all_maps[0]), vertex_partials(all_maps[1]), all_maps[2], all_maps[3]]
+    sums = [sum_oracle.wg_sum(sum_oracle.strided_sum(np.asarray(x, dtype=F32))) for x in flat]
     with np.errstate(divide='ignore', invalid='ignore'):
         return np.array([F32(s) / F32(m.size) for s, m in zip(sums, all_maps)], dtype=F32)
 

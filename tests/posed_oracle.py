@@ -80,45 +80,8 @@ def rodrigues_backward(pose, pose_mean, G, sincos, dtype=np.float32):
     return gd / a[:, None] + ga[:, None] * (e / a[:, None])
 
 
-# ---- the sums the stage shares with the template stage ----------------------------------------------------------------
-def _blend(coef, dirs, base, dt):
-    """base [M] + the sum over the rows of dirs [n, M] from +0.0 in ascending row."""
-    s = np.zeros(dirs.shape[1], dtype=dt)
-    for l in range(dirs.shape[0]):
-        s = s + coef[l] * dirs[l]
-    return base + s
-
-
-def _regress(reg, reg_dt, vs, dt):
-    """[J, 3]: every row of the regressor over its non-zeros, lanes then the tree."""
-    J = reg.shape[0]
-    Jr = np.zeros((J, 3), dtype=dt)
-    for j in range(J):
-        cols = np.nonzero(reg[j])[0]
-        vals = reg_dt[j, cols]
-        p = np.zeros((64, 3), dtype=dt)
-        for i0 in range(0, cols.size, 64):
-            n = min(64, cols.size - i0)
-            p[:n] = p[:n] + vals[i0:i0 + n, None] * vs[cols[i0:i0 + n]]
-        Jr[j] = body_oracle._tree_sum(p)
-    return Jr
-
-
-def _two_level(T, g, dt):
-    """[n]: sum_m T[l][m] g[m] over chunks of 256 (lanes, the tree per wave, the four waves), then the chunks in order."""
-    n, M = T.shape
-    chunks = -(-M // CHUNK)
-    gq = np.zeros(chunks * CHUNK, dtype=dt)
-    gq[:M] = g
-    Tp = np.zeros((n, chunks * CHUNK), dtype=dt)
-    Tp[:, :M] = T
-    q = (Tp * gq[None]).reshape(n, chunks, 4, 64)
-    q = body_oracle._tree_sum(np.moveaxis(q, 3, 0))
-    partial = ((q[..., 0] + q[..., 1]) + q[..., 2]) + q[..., 3]
-    out = np.zeros(n, dtype=dt)
-    for ch in range(chunks):
-        out = out + partial[:, ch]
-    return out
+# ---- the sums the stage shares with the template stage: body_oracle's ------------------------------------------------
+_blend, _regress, _two_level = body_oracle.blend, body_oracle.regress, body_oracle.two_level
 
 
 def _prepare(case, dt):
