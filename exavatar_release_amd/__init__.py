@@ -108,6 +108,13 @@ and for the face texture that ``MeshRenderer`` samples (``XY2UV`` and ``get_face
 ``fitting/common/nets/layer.py:9-23, 41-102``, ``fitting/main/unwrap.py:76-91``, ``fitting/common/utils/flame.py:46-73``):
 
     from exavatar_release_amd import XY2UV, get_face_index_map_uv, TextureUnwrap, uv_region_mask
+
+and for the mesh terms of the fitting loss (``EdgeLengthLoss``, ``FaceOffsetSymmetricReg``, ``PoseLoss`` and the centred
+vertex-to-vertex term: forward gathers, backwards over transposed tables built once, sums in a stated order, a zero
+gradient where the reference's zero-length edge gives NaN; reference ``fitting/common/nets/loss.py:73-87, 125-167``, called
+at ``fitting/main/model.py:224-250``):
+
+    from exavatar_release_amd import EdgeLengthLoss, FaceOffsetSymmetricReg, PoseLoss, centered_v2v_loss, flip_symmetry_plan
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -135,6 +142,8 @@ from .scene_gaussian import SceneGaussian
 from .lpips import LPIPS, lpips_distance
 from .offset_regs import JointOffsetSymmetricReg, OffsetRegs, loss_weights, offset_regs, symmetric_joint_pairs
 from .unwrap import XY2UV, TextureUnwrap, get_face_index_map_uv, uv_region_mask
+from .fit_terms import (EdgeLengthLoss, FaceOffsetSymmetricReg, FlipSymmetryPlan, PoseLoss, centered_v2v_loss,
+                        flip_symmetry_plan)
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -148,4 +157,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'PosedBodyOutput', 'FaceRGBLoss', 'face_composite', 'foreground_composite', 'Adam', 'adam_step',
            'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance',
            'OffsetRegs', 'offset_regs', 'JointOffsetSymmetricReg', 'symmetric_joint_pairs', 'loss_weights',
-           'XY2UV', 'get_face_index_map_uv', 'TextureUnwrap', 'uv_region_mask']
+           'XY2UV', 'get_face_index_map_uv', 'TextureUnwrap', 'uv_region_mask', 'EdgeLengthLoss',
+           'FaceOffsetSymmetricReg', 'PoseLoss', 'centered_v2v_loss', 'flip_symmetry_plan', 'FlipSymmetryPlan']

@@ -375,6 +375,17 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_offset_regs_vertex_forward': (ctypes.c_int, [_I32] * 3 + [c_void_p] * 10),
     'exa_mesh_offset_regs_joint_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 10),
     'exa_mesh_offset_regs_backward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 12 + [_PP, _PP] + [c_void_p] * 6),
+    # the mesh terms of the fitting loss (csrc/fit_terms.hip); the plan's arrays are host arrays
+    'exa_mesh_edge_length_forward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 6),
+    'exa_mesh_edge_length_backward': (ctypes.c_int, [_I32] * 5 + [c_void_p] * 9),
+    'exa_mesh_flip_symmetry_plan': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 8),
+    'exa_mesh_flip_symmetry_forward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 5),
+    'exa_mesh_flip_symmetry_backward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 8),
+    'exa_mesh_pose_loss_forward': (ctypes.c_int, [ctypes.c_int64] + [c_void_p] * 4),
+    'exa_mesh_pose_loss_backward': (ctypes.c_int, [ctypes.c_int64] + [c_void_p] * 5),
+    'exa_mesh_centered_v2v_blocks': (ctypes.c_int64, [_I32]),
+    'exa_mesh_centered_v2v_forward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 3 + [ctypes.c_float] + [c_void_p] * 4),
+    'exa_mesh_centered_v2v_backward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 3 + [ctypes.c_float] + [c_void_p] * 5),
 },_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUnwrap, ExaMeshUpsample,
             ExaMeshBody, ExaMeshPosed))
 

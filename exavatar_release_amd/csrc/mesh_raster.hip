@@ -33,6 +33,7 @@
 #include "../../include/exa_mesh.h"
 #include "abi_status.h"
 #include "fixed_sum.h"
+#include "index_transpose.h"
 
 namespace exa_mesh_impl {
 
@@ -617,16 +618,9 @@ int exa_mesh_workspace_sizes(int32_t N, int32_t F, int32_t H, int32_t W, ExaMesh
 int exa_mesh_vertex_faces(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* entries) {
     if (V < 0 || F < 0 || (int64_t)F * 3 > INT32_MAX) return fail(EXA_MESH_E_INVALID, "bad V / F");
     if (!offsets || (F > 0 && (!faces || !entries))) return fail(EXA_MESH_E_NULLPTR, "NULL argument");
-    for (int32_t v = 0; v <= V; ++v) offsets[v] = 0;
-    for (int64_t e = 0; e < (int64_t)F * 3; ++e) {
-        if (faces[e] < 0 || faces[e] >= V) return fail(EXA_MESH_E_INVALID, "face index out of range");
-        offsets[faces[e] + 1]++;
-    }
-    for (int32_t v = 0; v < V; ++v) offsets[v + 1] += offsets[v];
-    // ascending (face, corner) per vertex: walk the entries in order, each vertex's cursor starts at its offset
-    for (int64_t e = 0; e < (int64_t)F * 3; ++e) entries[offsets[faces[e]]++] = (int32_t)e;
-    for (int32_t v = V; v > 0; --v) offsets[v] = offsets[v - 1];
-    offsets[0] = 0;
+    // ascending (face, corner) per vertex: the shared index transpose (index_transpose.h)
+    if (exa::index_transpose(V, (int64_t)F * 3, faces, false, offsets, entries) >= 0)
+        return fail(EXA_MESH_E_INVALID, "face index out of range");
     return 0;
 }
 

@@ -17,6 +17,7 @@
 
 #include "../../include/exa_mesh.h"
 #include "abi_status.h"
+#include "index_transpose.h"
 
 namespace exa_mesh_impl {
 
@@ -211,22 +212,14 @@ int exa_mesh_neighbor_transpose(int32_t V, int32_t K, const int32_t* nbr_idx, in
     if (K < 1 || K > LAP_MAXK) return fail(EXA_MESH_E_INVALID, "K (neighbours per vertex) must be 1 .. 16");
     if ((int64_t)V * K > LAP_MAX_SLOTS) return fail(EXA_MESH_E_INVALID, "V * K exceeds 2^28");
     if (!offsets || (V > 0 && (!nbr_idx || !entries))) return fail(EXA_MESH_E_NULLPTR, "NULL argument");
-    const int64_t n = (int64_t)V * K;
-    for (int32_t v = 0; v <= V; ++v) offsets[v] = 0;
-    for (int64_t e = 0; e < n; ++e) {
-        if (nbr_idx[e] < 0 || nbr_idx[e] >= V) {
-            char what[128];
-            snprintf(what, sizeof(what), "neighbour index %d of vertex %d, slot %d is outside [0, %d)", (int)nbr_idx[e],
-                     (int)(e / K), (int)(e % K), (int)V);
-            return fail(EXA_MESH_E_INVALID, what);
-        }
-        offsets[nbr_idx[e] + 1]++;
+    // ascending (u, k) per vertex: the shared index transpose (index_transpose.h)
+    const int64_t e = exa::index_transpose(V, (int64_t)V * K, nbr_idx, false, offsets, entries);
+    if (e >= 0) {
+        char what[128];
+        snprintf(what, sizeof(what), "neighbour index %d of vertex %d, slot %d is outside [0, %d)", (int)nbr_idx[e],
+                 (int)(e / K), (int)(e % K), (int)V);
+        return fail(EXA_MESH_E_INVALID, what);
     }
-    for (int32_t v = 0; v < V; ++v) offsets[v + 1] += offsets[v];
-    // ascending (u, k) per vertex: walk the slots in order, each vertex's cursor starts at its offset
-    for (int64_t e = 0; e < n; ++e) entries[offsets[nbr_idx[e]]++] = (int32_t)e;
-    for (int32_t v = V; v > 0; --v) offsets[v] = offsets[v - 1];
-    offsets[0] = 0;
     return 0;
 }
 

@@ -45,6 +45,11 @@
  * `exa_mesh_unwrap` the reference's `XY2UV.forward` with the accumulation of fitting/main/unwrap.py:76-83
  * (layer.py:41-102), under `exavatar_release_amd.unwrap`.  Forward only.
  *
+ * And the mesh terms of the fitting program's loss: `exa_mesh_edge_length_*`, `exa_mesh_flip_symmetry_*`,
+ * `exa_mesh_pose_loss_*` and `exa_mesh_centered_v2v_*` are the reference's `EdgeLengthLoss`, `FaceOffsetSymmetricReg`,
+ * `PoseLoss` (fitting/common/nets/loss.py:73-87, 125-167) and the centred vertex-to-vertex term of
+ * fitting/main/model.py:235-237, under `exavatar_release_amd.fit_terms`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -887,6 +892,102 @@ int exa_mesh_offset_regs_backward(int32_t B, int32_t V, int32_t scale_offset_cha
                                   const float* const* dL_dmaps, const float* const* dL_dmeans, float* dL_dmean_offset,
                                   float* dL_dmean_offset_offset, float* dL_dscale, float* dL_dscale_offset,
                                   float* dL_djoint_offset, void* stream);
+
+/* ---- Mesh terms of the fitting loss (reference fitting/common/nets/loss.py:73-87, 125-167, fitting/main/model.py:235-237)
+ * EdgeLengthLoss, FaceOffsetSymmetricReg, PoseLoss and the centred vertex-to-vertex term.  Every operation is rounded in
+ * fp32 and never contracted; every sum runs in the order stated here.  No atomics, no memset: every output element is
+ * written by the launch that owns it.  sign(x) = (x > 0) - (x < 0), so sign(0) = 0.  Each backward gathers: the reference's
+ * index_put_(accumulate = True) scatters are replaced by per-element sums over a transposed table built once on the host.
+ *
+ * EDGE LENGTH.  coord_out [B, V, 3]; coord_gt [Bt, V, 3], Bt == B or 1; valid [Bv, V], Bv == B or 1; faces [F, 3] int32.
+ * Edge k of face f joins corners (a, b) = (0, 1), (0, 2), (1, 2) for k = 0, 1, 2.  For x = coord_out and x = coord_gt:
+ *     dx = x[a,0] - x[b,0], dy = x[a,1] - x[b,1], dz = x[a,2] - x[b,2];   d = sqrtf((dx * dx + dy * dy) + dz * dz)
+ *     loss[b, k F + f] = |d_out - d_gt| * (valid[a] * valid[b])                       ([B, 3 F]: the reference's cat order)
+ *   A face may repeat a vertex: that edge has d = 0.  A face index outside [0, V) reads nothing and gives NaN (the host
+ *   plan, exa_mesh_vertex_faces, refuses such a table first).
+ *   Backward, one sum per (b, v, c): acc = +0.0; for every slot (f, corner) of exa_mesh_vertex_faces' CSR that names v,
+ *   ascending f then corner, the two edges of that corner in ascending k (corner 0: k = 0, 1; corner 1: k = 0, 2; corner
+ *   2: k = 1, 2):
+ *     m = valid[a] * valid[b];   t = ((g[b, k F + f] * m) * sign(d_out - d_gt)) / d_out;   q = t * (x[a,c] - x[b,c])
+ *     acc = acc + q  where v is the edge's a,   acc = acc + (-q)  where it is the edge's b
+ *   AN EDGE WITH d_out == 0 CONTRIBUTES q = +0.0 (the reference divides 0 by 0 there and returns NaN: the one deliberate
+ *   deviation).  A vertex in no face gets +0.0.  coord_gt and valid get no gradient.
+ *
+ * FLIP SYMMETRY.  p = face_offset [B, Vf, 3].  The plan (exa_mesh_flip_symmetry_plan) holds for face row i, with
+ * v = face_vertex_idx[i]: tap[i,k] = the face row of vertex closest_faces[v,k], or -1 when that vertex carries no offset,
+ * and w[i,k] = bc[v,k].  r_k = p[b, tap[i,k], :], or (+0.0, +0.0, +0.0) for a tap of -1 (multiplied and added like any
+ * other); a tap outside [-1, Vf) reads nothing and gives NaN.
+ *     f_c = (r_0[c] * w[i,0] + r_1[c] * w[i,1]) + r_2[c] * w[i,2]
+ *     loss[b,i] = (|p[b,i,0] + f_0| + |p[b,i,1] - f_1|) + |p[b,i,2] - f_2|
+ *   Backward, one sum per (b, i, c), with s_0(j) = sign(p[b,j,0] + f_0(j)) * g[b,j], s_c(j) = sign(p[b,j,c] - f_c(j)) * g[b,j]
+ *   for c = 1, 2:  acc = s_c(i) first;  then for every (j, k) with tap[j,k] == i, ascending j then k (the plan's CSR, entry
+ *   3 j + k):  acc = acc + u_c(j) * w[j,k],  u_0 = s_0(j), u_c = -s_c(j) for c = 1, 2.
+ *
+ * POSE.  One thread per rotation n of N: R_out = matrix(quaternion(pose_out[n])), R_gt likewise, by steps 1 of the forward
+ * kinematics above (the small-angle branch below 1e-6 included); loss[n, q] = |R_out[q] - R_gt[q]|, q = 0 .. 8.  Backward:
+ * G[q] = g[n, q] * sign(R_out[q] - R_gt[q]), then the analytic Jacobian of step 1 (d angle / d x := 0 at a zero row).
+ * pose_gt gets no gradient.
+ *
+ * CENTRED V2V.  a = out, t = target [B, V, 3], w = weight [V], scale by value.  SUM2(x) over the V values of one (b, c):
+ * the vertices are cut into exa_mesh_centered_v2v_blocks(V) = ceil(V / 256) workgroups of EXA_MESH_FIT_ROWS = 256
+ * consecutive vertices, one per thread (+0.0 past the last), partial[g] = WG(values) of workgroup g (WG as defined for the
+ * offset regularisers above); then thread j of a workgroup: s = +0.0, s = s + partial[j], partial[j + 256], ..; SUM2 = WG(s).
+ *     ma[b,c] = SUM2(a[b,:,c]) / (float)V,  mt[b,c] = SUM2(t[b,:,c]) / (float)V        (means [B, 6]: ma, then mt)
+ *     e = (a - ma) - (t - mt);   loss[b,v,c] = (|e| * w[v]) * scale
+ *   Backward:  s = ((g * w[v]) * scale) * sign(e);   S[b,c] = SUM2(s[b,:,c]);   dL_dout = s - (S / (float)V).
+ *   target and weight get no gradient.
+ * B == 0 (and V, F, Vf, N == 0 where nothing is left to write) is a successful no-op in every call. */
+#define EXA_MESH_FIT_ROWS 256           /* threads per workgroup = vertices per partial of the centred term */
+
+/* One launch.  All [dev]; loss [B, 3 F], fully written. */
+int exa_mesh_edge_length_forward(int32_t B, int32_t Bt, int32_t Bv, int32_t V, int32_t F, const float* coord_out,
+                                 const float* coord_gt, const float* valid, const int32_t* faces, float* loss,
+                                 void* stream);
+
+/* One launch.  vert_offsets [dev] [V + 1], vert_entries [dev] [3 F]: exa_mesh_vertex_faces' CSR of `faces`; grad_loss
+ * [dev] [B, 3 F]; dL_dcoord_out [dev] [B, V, 3], fully written. */
+int exa_mesh_edge_length_backward(int32_t B, int32_t Bt, int32_t Bv, int32_t V, int32_t F, const float* coord_out,
+                                  const float* coord_gt, const float* valid, const int32_t* faces,
+                                  const int32_t* vert_offsets, const int32_t* vert_entries, const float* grad_loss,
+                                  float* dL_dcoord_out, void* stream);
+
+/* Host only, every array HOST memory.  face_vertex_idx [Vf]: the vertices of [0, V_full) that carry an offset, each named
+ * once; closest_faces [V_full, 3] int32 and bc [V_full, 3]: the reference's flip_corr.  Writes vertex_row [V_full] (the
+ * face row of every vertex, -1 for the others), taps [Vf, 3], weights [Vf, 3] and the taps' transpose offsets [Vf + 1],
+ * entries [3 Vf] (entry 3 j + k, ascending; offsets[Vf] of them are written).  EXA_MESH_E_INVALID, with a message naming
+ * it, for an index outside [0, V_full) in either table and for a vertex named twice in face_vertex_idx. */
+int exa_mesh_flip_symmetry_plan(int32_t V_full, int32_t Vf, const int32_t* face_vertex_idx, const int32_t* closest_faces,
+                                const float* bc, int32_t* vertex_row, int32_t* taps, float* weights, int32_t* offsets,
+                                int32_t* entries);
+
+/* One launch.  face_offset [dev] [B, Vf, 3]; taps, weights [dev] [Vf, 3]; loss [dev] [B, Vf], fully written. */
+int exa_mesh_flip_symmetry_forward(int32_t B, int32_t Vf, const float* face_offset, const int32_t* taps,
+                                   const float* weights, float* loss, void* stream);
+
+/* One launch.  offsets, entries [dev]: the plan's CSR; grad_loss [dev] [B, Vf]; dL_dface_offset [dev] [B, Vf, 3], fully
+ * written. */
+int exa_mesh_flip_symmetry_backward(int32_t B, int32_t Vf, const float* face_offset, const int32_t* taps,
+                                    const float* weights, const int32_t* offsets, const int32_t* entries,
+                                    const float* grad_loss, float* dL_dface_offset, void* stream);
+
+/* One launch each.  pose_out, pose_gt [dev] [N, 3]; loss, grad_loss [dev] [N, 9]; dL_dpose_out [dev] [N, 3]; fully written. */
+int exa_mesh_pose_loss_forward(int64_t N, const float* pose_out, const float* pose_gt, float* loss, void* stream);
+int exa_mesh_pose_loss_backward(int64_t N, const float* pose_out, const float* pose_gt, const float* grad_loss,
+                                float* dL_dpose_out, void* stream);
+
+/* The partials per (b, c) of the centred term: ceil(V / 256); 0 for V <= 0. */
+int64_t exa_mesh_centered_v2v_blocks(int32_t V);
+
+/* Two launches.  out, target [dev] [B, V, 3]; weight [dev] [V]; partials [dev] workspace of B * 6 * blocks floats, written
+ * before it is read; means [dev] [B, 6] and loss [dev] [B, V, 3], fully written. */
+int exa_mesh_centered_v2v_forward(int32_t B, int32_t V, const float* out, const float* target, const float* weight,
+                                  float scale, float* partials, float* means, float* loss, void* stream);
+
+/* Two launches.  means [dev] the forward's; grad_loss [dev] [B, V, 3]; partials [dev] workspace of B * 3 * blocks floats;
+ * dL_dout [dev] [B, V, 3], fully written (the first launch leaves s there, the second subtracts S / V in place). */
+int exa_mesh_centered_v2v_backward(int32_t B, int32_t V, const float* out, const float* target, const float* weight,
+                                   float scale, const float* means, const float* grad_loss, float* partials,
+                                   float* dL_dout, void* stream);
 
 #ifdef __cplusplus
 }
