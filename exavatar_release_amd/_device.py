@@ -120,10 +120,23 @@ def check_tensor(what, name, x, f32=True, rocm=False, on=None):
         raise ValueError('%s: %s is not on the device of %s' % (what, name, on[1]))
 
 
-def check_shape(what, name, x, shape, text):
+def check_shape(what, name, x, shape, text, shared=False):
+    """None in ``shape``: any extent.  ``shared``: the first extent may also be 1 (data that the whole batch shares)."""
     check_tensor(what, name, x)
-    if x.dim() != len(shape) or any(s is not None and x.shape[i] != s for i, s in enumerate(shape)):
+    if x.dim() != len(shape) or any(s is not None and x.shape[i] != s and not (shared and i == 0 and x.shape[0] == 1)
+                                    for i, s in enumerate(shape)):
         raise ValueError('%s: %s must be %s (it is %s)' % (what, name, text, tuple(x.shape)))
+
+
+def check_rows(what, name, x, V, shapes=None, text='[V], [V, 1] or [1, V, 1]'):
+    """Per-vertex data (by default a weight): a float32 tensor without a gradient in one of ``shapes``, which the message
+    names as ``text``; returns it contiguous in the first of them."""
+    check_tensor(what, name, x)
+    check_no_grad(what, name, x)
+    shapes = shapes or ((V,), (V, 1), (1, V, 1))
+    if tuple(x.shape) not in shapes:
+        raise ValueError('%s: %s must be %s with V = %d (it is %s)' % (what, name, text, V, tuple(x.shape)))
+    return x.reshape(shapes[0]).contiguous()
 
 
 def check_mask(what, name, m, V):

@@ -40,6 +40,7 @@ import torch.nn as nn
 
 from . import _lib, p3d_standins
 from ._device import _ptr, _workspace, check_no_grad, check_tensor, grad_in, launch
+from ._tables import host_i32, host_ptr
 from .kinematics import MAX_JOINTS, _tree
 
 MAX_COEF = 512           # EXA_MESH_BODY_MAX_COEF
@@ -51,26 +52,20 @@ BodyOutput = collections.namedtuple('BodyOutput', ['mesh_upsampled', 'mesh', 'jo
 _IP = ctypes.POINTER(ctypes.c_int32)
 
 
-def _host_i32(a):
-    return a.ctypes.data_as(_IP)
-
-
 def upsample_plan(faces, num_verts, subdivide_num):
     """The flat plan of ``subdivide_num`` rounds over ``faces`` [F, 3] (a contiguous int32 numpy array) as the library
     builds and validates it on the host: dict(V1, Vn, par, faces, off1, dep1, off2, dep2), numpy int32 arrays."""
     lib = _lib.load()
-    F = faces.shape[0]
-    counts = np.zeros(3, dtype=np.int32)
-    nul = _IP()
-    _lib.MESH.check(lib.exa_mesh_upsample_plan(num_verts, F, _host_i32(faces), subdivide_num, _host_i32(counts),
-                                               nul, nul, nul, nul, nul, nul))
+    F, counts = faces.shape[0], np.zeros(3, dtype=np.int32)
+    _lib.MESH.check(lib.exa_mesh_upsample_plan(num_verts, F, host_ptr(faces), subdivide_num, host_ptr(counts),
+                                               *(None,) * 6))
     V1, Vn, Fn = (int(c) for c in counts)
     plan = dict(par=np.zeros((Vn - num_verts, 2), np.int32), faces=np.zeros((Fn, 3), np.int32),
                 off1=np.zeros(num_verts + 1, np.int32), dep1=np.zeros(2 * (V1 - num_verts), np.int32),
                 off2=np.zeros(V1 + 1 if subdivide_num == 2 else 0, np.int32), dep2=np.zeros(2 * (Vn - V1), np.int32))
-    _lib.MESH.check(lib.exa_mesh_upsample_plan(num_verts, F, _host_i32(faces), subdivide_num, _host_i32(counts),
-                                               *(_host_i32(plan[k]) for k in ('par', 'faces', 'off1', 'dep1', 'off2',
-                                                                              'dep2'))))
+    _lib.MESH.check(lib.exa_mesh_upsample_plan(num_verts, F, host_ptr(faces), subdivide_num, host_ptr(counts),
+                                               *(plan[k].ctypes.data_as(_IP)      # given as a set: an empty one is not NULL
+                                                 for k in ('par', 'faces', 'off1', 'dep1', 'off2', 'dep2'))))
     plan.update(V1=V1, Vn=Vn)
     return plan
 
@@ -106,21 +101,20 @@ class MeshUpsampler(nn.Module):
     def __init__(self, faces, subdivide_num=2, num_verts=None):
         super(MeshUpsampler, self).__init__()
         what = 'MeshUpsampler'
+        device = torch.device('cpu')
         if isinstance(faces, torch.Tensor):
-            device = faces.device
-            faces = faces.detach().cpu().numpy()
-        else:
-            device = torch.device('cpu')
-            faces = np.asarray(faces)
+            device, faces = faces.device, faces.detach().cpu().numpy()
+        faces = np.asarray(faces)
         if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
             raise ValueError('%s: faces must be [F, 3] ints (it is %s %s)' % (what, faces.dtype, faces.shape))
         if subdivide_num not in (1, 2):
             raise ValueError('%s: subdivide_num must be 1 or 2 (it is %r)' % (what, subdivide_num))
-        if faces.size and (faces.min() < 0 or faces.max() >= 2 ** 31):
+        faces = host_i32(what, 'faces', faces, (None, 3))      # refuses what does not fit int32
+        if faces.size and faces.min() < 0:
             raise ValueError('%s: faces holds an index outside [0, 2^31)' % what)
         if num_verts is None:
             num_verts = int(faces.max()) + 1 if faces.size else 0
-        plan = upsample_plan(np.ascontiguousarray(faces, dtype=np.int32), int(num_verts), int(subdivide_num))
+        plan = upsample_plan(faces, int(num_verts), int(subdivide_num))
         self.subdivide_num = int(subdivide_num)
         self.num_coarse, self.num_mid, self.num_verts = int(num_verts), plan['V1'], plan['Vn']
         self.register_buffer('faces', torch.from_numpy(plan['faces'].astype(np.int64)).to(device), persistent=False)

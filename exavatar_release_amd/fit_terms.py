@@ -38,27 +38,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _workspace, check_devices, check_no_grad, check_shape, check_tensor, grad_in, launch
+from ._device import (_ptr, _workspace, check_devices, check_no_grad, check_rows, check_shape, check_tensor, grad_in,
+                      launch)
+from ._tables import face_tables, follow, host_i32, host_ptr
 
 ROWS = 256                # EXA_MESH_FIT_ROWS
-
-
-def _np_i32(what, name, x, shape):
-    """An index table as a contiguous int32 numpy array of ``shape`` (None: any length)."""
-    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if a.dtype.kind not in 'iu' and a.size:
-        raise ValueError('%s: %s must hold integers (it is %s)' % (what, name, a.dtype))
-    a = a.astype(np.int64)
-    if a.ndim != len(shape) or any(s is not None and a.shape[i] != s for i, s in enumerate(shape)):
-        raise ValueError('%s: %s must be %s (it is %s)' % (
-            what, name, '[' + ', '.join('n' if s is None else str(s) for s in shape) + ']', a.shape))
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError('%s: %s does not fit int32' % (what, name))
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
-def _host(a):
-    return a.ctypes.data if a.size else None
 
 
 # ---- EdgeLengthLoss ----------------------------------------------------------------------------------------------------
@@ -97,26 +81,20 @@ class EdgeLengthLoss(nn.Module):
     def __init__(self, face):
         super(EdgeLengthLoss, self).__init__()
         self.face = face
-        self._faces = _np_i32('EdgeLengthLoss', 'face', face, (None, 3))
+        self._faces = host_i32('EdgeLengthLoss', 'face', face, (None, 3))
         self._tables = {}     # (V, device) -> (faces, CSR offsets, CSR entries) on the device
 
     def _device_tables(self, V, device):
         hit = self._tables.get((V, device))
         if hit is None:
-            F = self._faces.shape[0]
-            offsets, entries = np.zeros(V + 1, dtype=np.int32), np.zeros(max(3 * F, 1), dtype=np.int32)
-            _lib.MESH.check(_lib.load().exa_mesh_vertex_faces(V, F, _host(self._faces), offsets.ctypes.data,
-                                                              entries.ctypes.data))
-            hit = self._tables[(V, device)] = tuple(torch.from_numpy(a).to(device) for a in (self._faces, offsets, entries))
+            hit = self._tables[(V, device)] = face_tables(self._faces, V, device)
         return hit
 
     def forward(self, coord_out, coord_gt, valid):
         what = 'EdgeLengthLoss'
         check_shape(what, 'coord_out', coord_out, (None, None, 3), '[B, V, 3]')
         B, V = coord_out.shape[:2]
-        check_tensor(what, 'coord_gt', coord_gt)
-        if coord_gt.dim() != 3 or tuple(coord_gt.shape[1:]) != (V, 3) or coord_gt.shape[0] not in (1, B):
-            raise ValueError('%s: coord_gt must be [%d, %d, 3] or [1, %d, 3] (it is %s)' % (what, B, V, V, tuple(coord_gt.shape)))
+        check_shape(what, 'coord_gt', coord_gt, (B, V, 3), '[%d, %d, 3] or [1, %d, 3]' % (B, V, V), shared=True)
         check_tensor(what, 'valid', valid)
         if tuple(valid.shape) not in ((V,), (1, V, 1), (B, V, 1)):
             raise ValueError('%s: valid must be [%d], [1, %d, 1] or [%d, %d, 1] (it is %s)' % (what, V, V, B, V, tuple(valid.shape)))
@@ -143,18 +121,17 @@ def flip_symmetry_plan(vertex_num, face_vertex_idx, closest_faces, bc):
     if isinstance(vertex_num, bool) or not isinstance(vertex_num, (int, np.integer)) or vertex_num < 0:
         raise ValueError('%s: vertex_num must be an integer >= 0 (it is %r)' % (what, vertex_num))
     V = int(vertex_num)
-    fvi = _np_i32(what, 'face_vertex_idx', face_vertex_idx, (None,))
-    cf = _np_i32(what, 'closest_faces', closest_faces, (V, 3))
+    fvi = host_i32(what, 'face_vertex_idx', face_vertex_idx, (None,))
+    cf = host_i32(what, 'closest_faces', closest_faces, (V, 3))
     w = bc.detach().cpu().numpy() if isinstance(bc, torch.Tensor) else np.asarray(bc)
     if w.shape != (V, 3) or w.dtype.kind != 'f':
         raise ValueError('%s: bc must be a floating [%d, 3] array (it is %s %s)' % (what, V, w.dtype, w.shape))
     w = np.ascontiguousarray(w, dtype=np.float32)
-    Vf = fvi.shape[0]
-    row = np.zeros(V, dtype=np.int32)
+    Vf, row = fvi.shape[0], np.zeros(V, dtype=np.int32)
     taps, weights = np.zeros((Vf, 3), dtype=np.int32), np.zeros((Vf, 3), dtype=np.float32)
     offsets, entries = np.zeros(Vf + 1, dtype=np.int32), np.zeros(max(3 * Vf, 1), dtype=np.int32)
-    _lib.MESH.check(_lib.load().exa_mesh_flip_symmetry_plan(V, Vf, _host(fvi), _host(cf), _host(w), _host(row), _host(taps),
-                                                            _host(weights), offsets.ctypes.data, entries.ctypes.data))
+    _lib.MESH.check(_lib.load().exa_mesh_flip_symmetry_plan(V, Vf, *(host_ptr(a) for a in (fvi, cf, w, row, taps, weights,
+                                                                                           offsets, entries))))
     return FlipSymmetryPlan(*(torch.from_numpy(a) for a in (row, taps, weights, offsets, entries[:max(int(offsets[Vf]), 1)])))
 
 
@@ -201,9 +178,7 @@ class FaceOffsetSymmetricReg(nn.Module):
         Vf = self.face_vertex_num
         check_shape(what, 'face_offset', face_offset, (None, Vf, 3), '[B, Vf, 3] with Vf = %d' % Vf)
         check_devices(what, 'face_offset', face_offset)
-        if self.taps.device != face_offset.device:
-            for name in self.PLAN:
-                setattr(self, name, getattr(self, name).to(face_offset.device))
+        follow(self, self.PLAN, face_offset.device)
         return _FlipSymmetry.apply(face_offset.contiguous(), self.taps, self.weights, self.tap_offsets, self.tap_entries)
 
 
@@ -294,12 +269,9 @@ def centered_v2v_loss(out, target, weight, scale=10.0):
     check_shape(what, 'out', out, (None, None, 3), '[B, V, 3]')
     B, V = out.shape[:2]
     check_shape(what, 'target', target, (B, V, 3), '[%d, %d, 3], the shape of out' % (B, V))
-    check_tensor(what, 'weight', weight)
-    if tuple(weight.shape) not in ((V,), (V, 1), (1, V, 1)):
-        raise ValueError('%s: weight must be [V], [V, 1] or [1, V, 1] with V = %d (it is %s)' % (what, V, tuple(weight.shape)))
+    weight_rows = check_rows(what, 'weight', weight, V)
     if isinstance(scale, (bool, torch.Tensor)) or not isinstance(scale, (int, float, np.floating, np.integer)):
         raise ValueError('%s: scale must be a Python number (it is %r)' % (what, type(scale).__name__))
     check_no_grad(what, 'target', target)
-    check_no_grad(what, 'weight', weight)
     check_devices(what, 'out', out, target=target, weight=weight)
-    return _CenteredV2V.apply(out.contiguous(), target.contiguous(), weight.reshape(V).contiguous(), float(scale))
+    return _CenteredV2V.apply(out.contiguous(), target.contiguous(), weight_rows, float(scale))

@@ -35,10 +35,11 @@ import torch
 
 from . import _lib
 from ._device import _ptr, check_tensor, grad_in, launch
+from ._tables import Cache
 
 MAX_JOINTS = 64           # EXA_MESH_KIN_MAX_JOINTS
 
-_trees = {}
+_trees = Cache()          # the parents as a tuple -> the validated host array
 
 
 def _tree(what, parents):
@@ -51,14 +52,14 @@ def _tree(what, parents):
         key = tuple(int(p) for p in parents)
     except (TypeError, ValueError):
         raise TypeError('%s: parents must be a sequence or a CPU tensor of ints' % what) from None
-    arr = _trees.get(key)
+    arr = _trees.find(key)
     if arr is None:
         if not 1 <= len(key) <= MAX_JOINTS:
             raise ValueError('%s: parents must name 1 .. %d joints (got %d)' % (what, MAX_JOINTS, len(key)))
         arr = (ctypes.c_int32 * len(key))(*key)
         depth = (ctypes.c_int32 * len(key))()
         _lib.MESH.check(_lib.load().exa_mesh_kinematics_depths(len(key), arr, depth))
-        _trees[key] = arr
+        _trees.keep(key, arr)
     return arr
 
 

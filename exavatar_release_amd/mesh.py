@@ -80,33 +80,25 @@ import torch.nn as nn
 
 from . import _lib
 from ._device import _ptr, grad_in, launch, need_rocm
+from ._tables import Cache, face_tables
 
 Fragments = collections.namedtuple('Fragments', ['pix_to_face', 'zbuf', 'bary_coords', 'dists'])
 Fragments.__doc__ = """pytorch3d ``Fragments`` of one face per pixel: ``pix_to_face`` [N,H,W,1] int64 (packed n * F + f, -1 for
 background), ``zbuf`` [N,H,W,1], ``bary_coords`` [N,H,W,1,3] (-1 for background), ``dists`` None (not computed)."""
 
-_topologies = {}     # (id(face), V, device) -> (host copy of face, faces [F,3] int32, CSR offsets, CSR entries)
+_topologies = Cache()     # (id(face), V, device) -> (host copy of face, (faces [F,3] int32, CSR offsets, CSR entries))
 
 
 def _topology(face, V, device):
     """``face`` as a device int32 [F,3] tensor plus the vertex -> (face, corner) CSR of the backward, built once per
-    topology: the cache is keyed on the object and checked against a host copy of its contents."""
+    topology: the cache is keyed on the object and checked against a host copy of its contents (numpy has no ``_version``)."""
     host = face.detach().cpu().numpy() if isinstance(face, torch.Tensor) else np.asarray(face)
     host = np.ascontiguousarray(host.reshape(-1, 3), dtype=np.int32)
     key = (id(face), int(V), str(device))
-    hit = _topologies.get(key)
+    hit = _topologies.find(key)
     if hit is not None and hit[0].shape == host.shape and np.array_equal(hit[0], host):
-        return hit[1:]
-    F = host.shape[0]
-    offsets = np.zeros(V + 1, dtype=np.int32)
-    entries = np.zeros(max(3 * F, 1), dtype=np.int32)
-    _lib.MESH.check(_lib.load().exa_mesh_vertex_faces(V, F, host.ctypes.data, offsets.ctypes.data, entries.ctypes.data))
-    entry = (host, torch.from_numpy(host).to(device), torch.from_numpy(offsets).to(device),
-             torch.from_numpy(entries).to(device))
-    if len(_topologies) > 16:
-        _topologies.clear()
-    _topologies[key] = entry
-    return entry[1:]
+        return hit[1]
+    return _topologies.keep(key, (host, face_tables(host, V, device)), face)[1]
 
 
 def _camera(cam_param, N, device):

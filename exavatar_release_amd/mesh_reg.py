@@ -37,7 +37,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _ptr, _workspace, check_no_grad, check_tensor, grad_in, launch
+from ._device import _ptr, _workspace, check_no_grad, check_rows, check_shape, check_tensor, grad_in, launch
+from ._tables import Cache, host_i32, host_ptr, stamp
 
 MAX_CHANNELS = 8          # EXA_MESH_LAP_MAX_CHANNELS
 MAX_NEIGHBORS = 16        # EXA_MESH_LAP_MAX_NEIGHBORS
@@ -72,16 +73,13 @@ def neighbor_table(vertex_num, face, neighbor_max_num=10):
 
 def _device_tables(idxs, weights, device):
     """(idx [V, K] int32, w [V, K] float32, CSR offsets [V + 1], CSR entries [V * K]) on ``device``."""
-    idx32 = np.ascontiguousarray(idxs.detach().cpu().numpy(), dtype=np.int64)
-    if idx32.size and (idx32.min() < 0 or idx32.max() >= idx32.shape[0]):
-        bad = idx32[(idx32 < 0) | (idx32 >= idx32.shape[0])][0]
-        raise ValueError('mesh_laplacian_loss: neighbour index %d is outside [0, %d)' % (bad, idx32.shape[0]))
-    idx32 = idx32.astype(np.int32)
+    idx32 = host_i32('mesh_laplacian_loss', 'neighbor_idxs', idxs, (None, None))
     V, K = idx32.shape
-    offsets = np.zeros(V + 1, dtype=np.int32)
-    entries = np.zeros(max(V * K, 1), dtype=np.int32)
-    _lib.MESH.check(_lib.load().exa_mesh_neighbor_transpose(V, K, idx32.ctypes.data, offsets.ctypes.data,
-                                                            entries.ctypes.data))
+    bad = idx32[(idx32 < 0) | (idx32 >= V)]
+    if bad.size:      # a ValueError here; the library would refuse it too, as a RuntimeError
+        raise ValueError('mesh_laplacian_loss: neighbour index %d is outside [0, %d)' % (bad[0], V))
+    offsets, entries = np.zeros(V + 1, dtype=np.int32), np.zeros(max(V * K, 1), dtype=np.int32)
+    _lib.MESH.check(_lib.load().exa_mesh_neighbor_transpose(V, K, host_ptr(idx32), host_ptr(offsets), host_ptr(entries)))
     return (torch.from_numpy(idx32).to(device), weights.detach().to(device=device, dtype=torch.float32).contiguous(),
             torch.from_numpy(offsets).to(device), torch.from_numpy(entries).to(device))
 
@@ -124,22 +122,17 @@ def _check_inputs(out, target, weight, V, what):
         if x is not None:
             check_tensor(what, name, x, rocm=True, on=(out, 'out'))
     check_no_grad(what, 'target', target)
-    check_no_grad(what, 'weight', weight)
     if out.dim() != 3 or out.shape[1] != V or not 1 <= out.shape[2] <= MAX_CHANNELS:
         raise ValueError('%s: out must be [B, V, C] with V = %d and 1 <= C <= %d (it is %s)'
                          % (what, V, MAX_CHANNELS, tuple(out.shape)))
-    if target is not None and (target.dim() != 3 or tuple(target.shape[1:]) != tuple(out.shape[1:])
-                               or target.shape[0] not in (1, out.shape[0])):
-        raise ValueError('%s: target must be [B, V, C] or [1, V, C] like out (it is %s)' % (what, tuple(target.shape)))
+    if target is not None:
+        check_shape(what, 'target', target, out.shape, '[B, V, C] or [1, V, C] like out', shared=True)
     if weight is not None:
-        if tuple(weight.shape) not in ((V,), (1, V, 1), (V, 1)):
-            raise ValueError('%s: weight must be [V], [1, V, 1] or [V, 1] with V = %d (it is %s)'
-                             % (what, V, tuple(weight.shape)))
-        weight = weight.reshape(V).contiguous()
+        weight = check_rows(what, 'weight', weight, V, ((V,), (1, V, 1), (V, 1)), '[V], [1, V, 1] or [V, 1]')
     return out.contiguous(), None if target is None else target.contiguous(), weight
 
 
-_tables = {}     # functional form: (id(idxs), id(weights), their versions and storage, device) -> (idxs, weights, tables)
+_tables = Cache()     # functional form: (stamp of idxs and weights, device) -> the four device tables
 
 
 def mesh_laplacian_loss(out, target, neighbor_idxs, neighbor_weights, weight=None, return_d=False):
@@ -155,15 +148,10 @@ def mesh_laplacian_loss(out, target, neighbor_idxs, neighbor_weights, weight=Non
                          % (what, MAX_NEIGHBORS))
     check_no_grad(what, 'neighbor_weights', neighbor_weights)
     out, target, weight = _check_inputs(out, target, weight, neighbor_idxs.shape[0], what)
-    key = (id(neighbor_idxs), id(neighbor_weights), neighbor_idxs._version, neighbor_weights._version,
-           neighbor_idxs.data_ptr(), neighbor_weights.data_ptr(), str(out.device))
-    hit = _tables.get(key)
-    if hit is None:
-        if len(_tables) > 16:
-            _tables.clear()
-        # the entry holds the two tensors, so that their ids stay theirs while it lives
-        hit = _tables[key] = (neighbor_idxs, neighbor_weights, _device_tables(neighbor_idxs, neighbor_weights, out.device))
-    loss, d = _Laplacian.apply(out, target, weight, *hit[2])
+    key = stamp(neighbor_idxs, neighbor_weights) + (str(out.device),)
+    tables = _tables.find(key) or _tables.keep(key, _device_tables(neighbor_idxs, neighbor_weights, out.device),
+                                               neighbor_idxs, neighbor_weights)
+    loss, d = _Laplacian.apply(out, target, weight, *tables)
     return (loss, d) if return_d else loss
 
 

@@ -34,15 +34,14 @@ pairs) gives an empty map or a NaN mean, as ``torch.mean`` of an empty tensor do
 allocate their outputs with torch and neither allocate nor synchronise inside the library, so forward and backward can
 be captured into a hipGraph.
 """
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import (_ptr, _ptrs, _workspace, check_devices, check_mask, check_no_grad, check_reduce, check_shape,
-                      check_tensor, grad_in, launch)
+from ._device import (_ptr, _ptrs, _workspace, check_devices, check_mask, check_no_grad, check_reduce, check_rows,
+                      check_shape, check_tensor, grad_in, launch)
+from ._tables import Cache, follow, host_i32, host_ptr
 
 TERMS = ('gaussian_mean_reg', 'gaussian_scale_reg', 'joint_offset_reg', 'joint_offset_sym_reg')      # model.py's key order
 ROWS = 256                # EXA_MESH_OFFSET_ROWS
@@ -74,14 +73,13 @@ def _pair_tables(sym_pairs, J, what):
         raise ValueError('%s: sym_pairs names joint %d outside [0, %d)' % (what, bad[0], J))
     if len(set(right + left)) != 2 * len(right):
         raise ValueError('%s: sym_pairs names a joint twice; a joint belongs to at most one pair' % what)
-    r, l = np.asarray(right, dtype=np.int32).reshape(-1), np.asarray(left, dtype=np.int32).reshape(-1)
+    r, l = host_i32(what, 'sym_pairs', right, (None,)), host_i32(what, 'sym_pairs', left, (None,))
     table = np.zeros(J, dtype=np.int32)
-    as_ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))      # noqa: E731
-    _lib.MESH.check(_lib.load().exa_mesh_offset_regs_pair_table(J, len(right), as_ip(r), as_ip(l), as_ip(table)))
+    _lib.MESH.check(_lib.load().exa_mesh_offset_regs_pair_table(J, len(right), host_ptr(r), host_ptr(l), host_ptr(table)))
     return torch.from_numpy(r), torch.from_numpy(l), torch.from_numpy(table)
 
 
-_pair_cache = {}     # functional form: (right, left, J, device) -> the three device tables
+_pair_cache = Cache()     # functional form: (right, left, J, device) -> the three device tables
 
 
 def _device_pairs(sym_pairs, J, device, what):
@@ -92,12 +90,7 @@ def _device_pairs(sym_pairs, J, device, what):
     except (TypeError, ValueError, IndexError):
         raise ValueError('%s: sym_pairs must be (right indices, left indices), as symmetric_joint_pairs returns them' % what)
     key = (key, J, str(device))
-    hit = _pair_cache.get(key)
-    if hit is None:
-        if len(_pair_cache) > 16:
-            _pair_cache.clear()
-        hit = _pair_cache[key] = tuple(t.to(device) for t in _pair_tables(key[0], J, what))
-    return hit
+    return _pair_cache.find(key) or _pair_cache.keep(key, tuple(t.to(device) for t in _pair_tables(key[0], J, what)))
 
 
 # ---- the node ----------------------------------------------------------------------------------------------------------
@@ -156,14 +149,6 @@ class _OffsetRegs(torch.autograd.Function):
 
 
 # ---- argument checks: tensor, dtype, shape, then the device ------------------------------------------------------------
-def _weight_rows(what, name, w, V):
-    check_tensor(what, name, w)
-    check_no_grad(what, name, w)
-    if tuple(w.shape) not in ((V,), (V, 1), (1, V, 1)):
-        raise ValueError('%s: %s must be [V], [V, 1] or [1, V, 1] with V = %d (it is %s)' % (what, name, V, tuple(w.shape)))
-    return w.reshape(V).contiguous()
-
-
 def offset_regs(mean_offset, mean_offset_offset, scale, scale_offset, joint_offset, mean_weight, scale_weight,
                 joint_offset_ref, joint_weight, sym_pairs, reduce='mean'):
     """The four terms for a caller's own constants: a dict in ``TERMS`` order (module docstring).  ``mean_weight``,
@@ -183,8 +168,8 @@ def offset_regs(mean_offset, mean_offset_offset, scale, scale_offset, joint_offs
                          % (what, B, V, B, V, tuple(scale_offset.shape)))
     check_shape(what, 'joint_offset', joint_offset, (None, 3), '[J, 3]')
     J = joint_offset.shape[0]
-    w_mean = _weight_rows(what, 'mean_weight', mean_weight, V)
-    w_scale = _weight_rows(what, 'scale_weight', scale_weight, V)
+    w_mean = check_rows(what, 'mean_weight', mean_weight, V)
+    w_scale = check_rows(what, 'scale_weight', scale_weight, V)
     for name, x in (('joint_offset_ref', joint_offset_ref), ('joint_weight', joint_weight)):
         check_shape(what, name, x, (J, 3), '[J, 3] with J = %d' % J)
         check_no_grad(what, name, x)
@@ -212,8 +197,8 @@ class OffsetRegs(nn.Module):
         what = 'OffsetRegs'
         check_tensor(what, 'mean_weight', mean_weight)
         V = mean_weight.numel()
-        w_mean = _weight_rows(what, 'mean_weight', mean_weight, V)
-        w_scale = _weight_rows(what, 'scale_weight', scale_weight, V)
+        w_mean = check_rows(what, 'mean_weight', mean_weight, V)
+        w_scale = check_rows(what, 'scale_weight', scale_weight, V)
         check_shape(what, 'joint_offset_ref', joint_offset_ref, (None, 3), '[J, 3]')
         J = joint_offset_ref.shape[0]
         check_shape(what, 'joint_weight', joint_weight, (J, 3), '[J, 3] with J = %d' % J)
@@ -253,10 +238,7 @@ class JointOffsetSymmetricReg(nn.Module):
         what = 'JointOffsetSymmetricReg'
         check_shape(what, 'joint_offset', joint_offset, (self.joint_num, 3), '[J, 3] with J = %d' % self.joint_num)
         check_devices(what, 'joint_offset', joint_offset)
-        dev = joint_offset.device
-        if self.joint_pair.device != dev:                        # a module that was never moved: the tables follow the input
-            for name in ('pair_right', 'pair_left', 'joint_pair'):
-                setattr(self, name, getattr(self, name).to(dev))
+        follow(self, ('joint_pair', 'pair_right', 'pair_left'), joint_offset.device)
         rows, none = joint_offset.new_empty((0, 0, 3)), joint_offset.new_empty((0,))
         unset = joint_offset.new_empty((self.joint_num, 3))     # term 2's constants: its map is computed and dropped
         return _OffsetRegs.apply(rows, rows, rows, rows, joint_offset.contiguous(), none, none, unset, unset,

@@ -55,8 +55,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import (_ptr, _workspace, check_devices, check_mask, check_no_grad, check_shape, check_tensor, grad_in,
-                      launch)
+from ._device import _ptr, _workspace, check_devices, check_mask, check_no_grad, check_rows, check_shape, grad_in, launch
+from ._tables import Cache, stamp
 
 MAX_TOP_K = 64            # EXA_MESH_ARM_MAX_K
 ARM_WAVES = 8             # EXA_MESH_ARM_WAVES
@@ -67,11 +67,7 @@ CHUNK = 256               # EXA_MESH_REG_CHUNK
 
 # ---- argument checks: dtype and shape first, the device last, each a ValueError naming the argument -------------------
 def _normal_rows(what, normal, V):
-    check_tensor(what, 'normal', normal)
-    check_no_grad(what, 'normal', normal)
-    if tuple(normal.shape) not in ((V, 3), (1, V, 3)):
-        raise ValueError('%s: normal must be [V, 3] or [1, V, 3] with V = %d (it is %s)' % (what, V, tuple(normal.shape)))
-    return normal.reshape(V, 3).contiguous()
+    return check_rows(what, 'normal', normal, V, ((V, 3), (1, V, 3)), '[V, 3] or [1, V, 3]')
 
 
 def _normals_of(mesh, face):
@@ -198,10 +194,6 @@ def arm_rgb_loss(plan, rgb, return_d=False):
     return (loss, d) if return_d else loss
 
 
-def _identity(*tensors):
-    return tuple((id(t), t._version, t.data_ptr()) for t in tensors)
-
-
 class ArmRGBReg(nn.Module):
     """Drop-in for the reference's ``ArmRGBReg`` (``loss.py:173-197``): same ``forward`` signature, ``[B, L, 3]`` result.
     ``dist_x_thr`` and ``top_k`` are the reference's constants.  ``plan`` is the plan of the last call."""
@@ -210,12 +202,12 @@ class ArmRGBReg(nn.Module):
         super(ArmRGBReg, self).__init__()
         self.dist_x_thr, self.top_k = dist_x_thr, top_k
         self.plan = None
-        self._key = None     # (identity of the three inputs, the inputs themselves: their ids stay theirs while it lives)
+        self._key = None     # (stamp of the three inputs and the two constants, the inputs themselves)
 
     def forward(self, mesh_neutral_pose, is_upper_arm, is_lower_arm, rgb):
         key = None
         if all(isinstance(t, torch.Tensor) for t in (mesh_neutral_pose, is_upper_arm, is_lower_arm)):
-            key = _identity(mesh_neutral_pose, is_upper_arm, is_lower_arm) + (self.dist_x_thr, self.top_k)
+            key = stamp(mesh_neutral_pose, is_upper_arm, is_lower_arm) + (self.dist_x_thr, self.top_k)
         if self.plan is None or key is None or self._key is None or self._key[0] != key:
             self.plan = arm_neighbors(mesh_neutral_pose, is_upper_arm, is_lower_arm, self.dist_x_thr, self.top_k)
             self._key = (key, mesh_neutral_pose, is_upper_arm, is_lower_arm)
@@ -260,19 +252,13 @@ def index_tables(mask):
     return idx, rank
 
 
-_hand_tables = {}     # identity of the two masks -> (the masks, {'r': tables, 'l': tables, 'h': tables of the union})
+_hand_tables = Cache()     # stamp of the two masks -> {'r': tables, 'l': tables, 'h': tables of the union}
 
 
 def _hands(is_rhand, is_lhand):
-    key = _identity(is_rhand, is_lhand)
-    hit = _hand_tables.get(key)
-    if hit is None:
-        if len(_hand_tables) > 16:
-            _hand_tables.clear()
-        # the entry holds the two tensors, so that their ids stay theirs while it lives
-        hit = _hand_tables[key] = (is_rhand, is_lhand, {'r': index_tables(is_rhand), 'l': index_tables(is_lhand),
-                                                        'h': index_tables(is_rhand | is_lhand)})
-    return hit[2]
+    key = stamp(is_rhand, is_lhand)
+    return _hand_tables.find(key) or _hand_tables.keep(key, {'r': index_tables(is_rhand), 'l': index_tables(is_lhand),
+                                                             'h': index_tables(is_rhand | is_lhand)}, is_rhand, is_lhand)
 
 
 # ---- HandRGBReg --------------------------------------------------------------------------------------------------------
