@@ -115,6 +115,13 @@ gradient where the reference's zero-length edge gives NaN; reference ``fitting/c
 at ``fitting/main/model.py:224-250``):
 
     from exavatar_release_amd import EdgeLengthLoss, FaceOffsetSymmetricReg, PoseLoss, centered_v2v_loss, flip_symmetry_plan
+
+and for the keypoints of that loss (``BodyKeypoints``: the extra joints and the static and dynamic landmarks of the SMPL-X /
+FLAME layer with the camera tail of ``get_smplx_coord`` / ``get_flame_coord``; ``CoordLoss``: the hand-box rule as one launch
+without a read-back; reference ``smplx/body_models.py:1257-1283``, ``fitting/main/model.py:97-117, 140-157``,
+``fitting/common/nets/loss.py:9-71``):
+
+    from exavatar_release_amd import BodyKeypoints, KeypointOutput, CoordLoss
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, config,
                          rasterize_gaussians, rasterize_gaussians_batch)
@@ -144,6 +151,7 @@ from .offset_regs import JointOffsetSymmetricReg, OffsetRegs, loss_weights, offs
 from .unwrap import XY2UV, TextureUnwrap, get_face_index_map_uv, uv_region_mask
 from .fit_terms import (EdgeLengthLoss, FaceOffsetSymmetricReg, FlipSymmetryPlan, PoseLoss, centered_v2v_loss,
                         flip_symmetry_plan)
+from .keypoints import BodyKeypoints, CoordLoss, KeypointOutput
 
 __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRenderer', 'rasterize_gaussians',
            'rasterize_gaussians_batch', 'config', 'track_densify_stats', 'render_many', 'render_views',
@@ -158,4 +166,5 @@ __all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'GaussianRende
            'SceneGaussian', 'DensifyPlan', 'densify_plan', 'densify_apply', 'prune_plan', 'LPIPS', 'lpips_distance',
            'OffsetRegs', 'offset_regs', 'JointOffsetSymmetricReg', 'symmetric_joint_pairs', 'loss_weights',
            'XY2UV', 'get_face_index_map_uv', 'TextureUnwrap', 'uv_region_mask', 'EdgeLengthLoss',
-           'FaceOffsetSymmetricReg', 'PoseLoss', 'centered_v2v_loss', 'flip_symmetry_plan', 'FlipSymmetryPlan']
+           'FaceOffsetSymmetricReg', 'PoseLoss', 'centered_v2v_loss', 'flip_symmetry_plan', 'FlipSymmetryPlan',
+           'BodyKeypoints', 'KeypointOutput', 'CoordLoss']

@@ -175,6 +175,15 @@ class ExaMeshPosed(ctypes.Structure):
                 ('weights', c_void_p)]
 
 
+class ExaMeshKeypoints(ctypes.Structure):
+    """The tables of one keypoint selection (include/exa_mesh.h); every pointer is a device pointer."""
+    _fields_ = [('V', ctypes.c_int32), ('J', ctypes.c_int32), ('K', ctypes.c_int32), ('Ld', ctypes.c_int32),
+                ('C', ctypes.c_int32), ('T', ctypes.c_int32),
+                ('rec', c_void_p), ('rec_w', c_void_p), ('dyn_vtx', c_void_p), ('dyn_w', c_void_p), ('chain', c_void_p),
+                ('vrow', c_void_p), ('voff', c_void_p), ('vent_k', c_void_p), ('vent_bin', c_void_p), ('vent_w', c_void_p),
+                ('joff', c_void_p), ('jent', c_void_p)]
+
+
 class ExaMlpNet(ctypes.Structure):
     """exa_mlp_net (include/exa_mlp.h): the arrays hold EXA_MLP_MAX_HEADS = 4 heads and EXA_MLP_MAX_LAYERS = 4 layers."""
     _fields_ = [('n_layers', ctypes.c_int32), ('in_width', ctypes.c_int32), ('shared_width', ctypes.c_int32),
@@ -230,6 +239,7 @@ _UP = ctypes.POINTER(ExaMeshUpsample)
 _BP = ctypes.POINTER(ExaMeshBody)
 _PBP = ctypes.POINTER(ExaMeshPosed)
 _U64P = ctypes.POINTER(ctypes.c_uint64)
+_KP = ctypes.POINTER(ExaMeshKeypoints)
 
 # ---- the six ABIs
 # the Gaussian rasterizer with its image losses (exa_ssim_*, exa_photo_*, exa_l1_* report through exa_raster_last_error)
@@ -386,8 +396,16 @@ MESH =Abi('exa_mesh', 'exa_mesh.h', 100, {
     'exa_mesh_centered_v2v_blocks': (ctypes.c_int64, [_I32]),
     'exa_mesh_centered_v2v_forward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 3 + [ctypes.c_float] + [c_void_p] * 4),
     'exa_mesh_centered_v2v_backward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 3 + [ctypes.c_float] + [c_void_p] * 5),
+    # the keypoints of the fitting and CoordLoss (csrc/keypoints.hip)
+    'exa_mesh_keypoints_blocks': (ctypes.c_int64, [_I32]),
+    'exa_mesh_keypoints_workspace_size': (ctypes.c_int, [_I32, _I32, _I32, _U64P]),
+    'exa_mesh_keypoints_forward': (ctypes.c_int, [_KP, _I32] + [c_void_p] * 6 + [_I32] + [c_void_p] * 6),
+    'exa_mesh_keypoints_backward': (ctypes.c_int, [_KP, _I32] + [c_void_p] * 5 + [_I32] + [c_void_p] * 6 + [_U64]
+                                    + [c_void_p] * 4),
+    'exa_mesh_coord_loss_forward': (ctypes.c_int, [_I32] * 4 + [c_void_p] * 11),
+    'exa_mesh_coord_loss_backward': (ctypes.c_int, [_I32, _I32] + [c_void_p] * 8),
 },_by_name(ExaMeshGeometry, ExaMeshTexture, ExaMeshWorkspaceSizes, ExaMeshShading, ExaMeshUnwrap, ExaMeshUpsample,
-            ExaMeshBody, ExaMeshPosed))
+            ExaMeshBody, ExaMeshPosed, ExaMeshKeypoints))
 
 # the K-nearest-neighbour search
 KNN = Abi('exa_knn', 'exa_knn.h', 100, {

@@ -61,6 +61,8 @@ SOURCES = {
     'offset_regs.hip': ['-ffp-contract=off'],
     # the mesh terms of the fitting loss are defined operation by operation (include/exa_mesh.h)
     'fit_terms.hip': ['-ffp-contract=off'],
+    # the keypoints of the fitting and CoordLoss are defined operation by operation (include/exa_mesh.h)
+    'keypoints.hip': ['-ffp-contract=off'],
     # the face-texture unwrap's sample position and blend are defined operation by operation (include/exa_mesh.h)
     'unwrap.hip': ['-ffp-contract=off'],
     # the scene-Gaussian stage and its backward are defined operation by operation (include/exa_raster.h)

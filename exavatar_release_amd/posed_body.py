@@ -23,9 +23,10 @@ operation is rounded in fp32 without fused multiply-adds, every sum runs in an o
 tables alone, and no kernel uses an atomic: the same inputs give the same bits, forward and backward.  ``sinf`` / ``cosf``
 are the only transcendentals.
 
-Not covered: the extra joints of ``vertex_joint_selector``, the static and dynamic landmarks, ``joint_mapper``, PCA
-hands, ``locator_offset`` and a gradient to ``face_offset`` (the avatar code reads only ``output.vertices``); batches of
-frames per call; the fitting pipeline under ``fitting/``.
+The extra joints of ``vertex_joint_selector`` and the static and dynamic landmarks -- the rest of the layer's ``joints`` --
+are ``exavatar_release_amd.keypoints.BodyKeypoints``, which takes this stage's ``vertices``, ``joints`` and ``rot`` stacked
+over the frames.  Not covered: ``joint_mapper``, PCA hands, ``locator_offset`` and a gradient to ``face_offset`` (the avatar
+code reads only ``output.vertices``); batches of frames per call.
 """
 import collections
 import ctypes

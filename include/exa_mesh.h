@@ -50,6 +50,11 @@
  * `PoseLoss` (fitting/common/nets/loss.py:73-87, 125-167) and the centred vertex-to-vertex term of
  * fitting/main/model.py:235-237, under `exavatar_release_amd.fit_terms`.
  *
+ * And the keypoints of that loss: `exa_mesh_keypoints_*` are the tail of the SMPL-X layer (extra joints, static and dynamic
+ * landmarks; smplx/body_models.py:1257-1283) with the tail of `get_smplx_coord` / `get_flame_coord`
+ * (fitting/main/model.py:97-117, 140-157), and `exa_mesh_coord_loss_*` the reference's `CoordLoss`
+ * (fitting/common/nets/loss.py:9-71), under `exavatar_release_amd.keypoints`.
+ *
  * Conventions (those of exa_raster.h)
  *   - plain C types only: device pointers, sizes, a `hipStream_t` passed as `void*`.
  *   - every pointer marked [dev] is a device pointer owned by the caller; the library allocates nothing and keeps no
@@ -988,6 +993,117 @@ int exa_mesh_centered_v2v_forward(int32_t B, int32_t V, const float* out, const 
 int exa_mesh_centered_v2v_backward(int32_t B, int32_t V, const float* out, const float* target, const float* weight,
                                    float scale, const float* means, const float* grad_loss, float* partials,
                                    float* dL_dout, void* stream);
+
+/* ---- Keypoints of the fitting (reference smplx/body_models.py:1257-1283, lbs.py:30-153, vertex_joint_selector.py:73-80;
+ * fitting/main/model.py:97-117, 140-157; CoordLoss, fitting/common/nets/loss.py:9-71).  Every operation is rounded in fp32 and
+ * never contracted (a landmark row's two fmaf are stated as such); every sum runs in the order stated here.  No atomics, no
+ * memset: every output element is written by the
+ * launch that owns it, so the same inputs give the same bits on every call.
+ *
+ * KEYPOINTS.  vertices [B, V, 3], joints [B, J, 3], rot [B, J, 3, 3], trans [B, 3] or NULL, focal, princpt [B, 2].  The host
+ * compiles the selection into K + 1 records rec [K + 1, 4] int32 = (kind, i0, i1, i2), record K being the root:
+ *     EXA_MESH_KPT_JOINT    raw = joints[b, i0]                                              (a copy)
+ *     EXA_MESH_KPT_VERTEX   raw = vertices[b, i0]                                            (a copy)
+ *     EXA_MESH_KPT_STATIC   raw[c] = fmaf(x[i2,c], w2, fmaf(x[i1,c], w1, x[i0,c] * w0)),  x = vertices[b], w = rec_w[k, 0..2]:
+ *                           one rounded product and two FUSED multiply-adds, the only fused operations of this stage.  It is
+ *                           the order in which the reference's einsum('blfi,blf->bli') sums over f on the device (a dot
+ *                           product with a fused accumulator, measured at seven shapes from 12 to 13 056 coordinates without
+ *                           one differing bit), so that the rows equal the reference's expressions in torch bit for bit
+ *     EXA_MESH_KPT_DYNAMIC  the same with (i0, i1, i2) = dyn_vtx[bin, slot], w = dyn_w[bin, slot], slot = rec's i0, bin = the
+ *                           item's yaw bin; dyn_vtx, dyn_w are [EXA_MESH_KPT_BINS, Ld, 3]
+ *   An index outside its table reads nothing and gives NaN (the host refuses such a table first).
+ *   Yaw bin (only with Ld > 0, else 0; rot takes no gradient).  rel = identity; for i = 0 .. C - 1: rel = rot[b, chain[i]] . rel,
+ *   each element (R[r,0] * rel[0,c] + R[r,1] * rel[1,c]) + R[r,2] * rel[2,c].  sy = sqrtf(rel00 * rel00 + rel10 * rel10),
+ *   a = atan2f(-rel20, sy), deg = ((-a) * 180.0f) / (float)pi.  A deg that is not finite gives bin 0.  y = rintf(min(deg, 39))
+ *   (half to even); bin = y for y >= 0, 39 - y for -39 <= y < 0, 78 for y < -39; clamped into [0, 78] before any table read.
+ *   root = raw(record K);  cam = (raw - root) + trans  (trans NULL: no addition);
+ *   kpt_proj = ((cam_x / cam_z) * focal_x) + princpt_x, likewise y: IEEE division, cam_z == 0 included;
+ *   kpt_cam = cam, or cam - trans with root_rel;  mesh_cam = (vertices - root) + trans, then - trans with root_rel.
+ *   Backward.  Cotangents g_cam [B, K, 3], g_proj [B, K, 2], g_root [B, 3], g_mesh [B, V, 3], each possibly NULL (= zeros).
+ *   Per keypoint, with cam recomputed as above: tx = g_proj_x * focal_x, ty = g_proj_y * focal_y, qx = cam_x / cam_z,
+ *   qy = cam_y / cam_z;  p = (tx / cam_z, ty / cam_z, -((tx * qx + ty * qy) / cam_z)), or +0 without g_proj;
+ *   c_k = g_cam + p (just g_cam, or just p, when the other is NULL).  S_c = sum of c_k, S_p = sum of p_k: s = +0.0, s = s + x_k
+ *   for k = 0 .. K - 1.  S_m[c] = SUM2 of g_mesh[b, :, c] exactly as the centred term above (workgroups of EXA_MESH_KPT_ROWS
+ *   = 256 vertices, exa_mesh_keypoints_blocks(V) partials), +0.0 without g_mesh.
+ *     r_K (the root's raw cotangent) = (g_root - S_c) - S_m;   r_k = c_k for k < K
+ *     d_trans = S_c + S_m, or S_p with root_rel (the camera coordinates' own + trans - trans cancels exactly)
+ *     d_joints[b, j] = +0.0, then + r_k for the records k = 0 .. K that name joint j, ascending (joff / jent)
+ *     d_vertices[b, v] = g_mesh[b, v] (+0.0 without), then acc = acc + w * r_k for the entries (k, corner, bin) of v in
+ *       ascending (k, corner, bin) (vrow / voff / vent_*): those with bin == -1 (static; a vertex record has w = 1) and those
+ *       whose bin is the item's yaw bin.
+ *   No gradient to rot, focal or princpt.
+ *
+ * COORD LOSS.  kpt_proj, kpt_proj_gt [B, K, 2], kpt_valid [B, K] (assumed >= 0), kpt_cam [B, K, 3], weight [B, K, 2] or NULL.
+ * Per item and hand (index list idx [n]): sum = +0.0, sum = sum + valid[idx[i]] for i = 0 .. n - 1; z likewise over
+ * cam[idx[i], 2], depth = z / (float)n; over the entries with valid > 0, in order, min and max of x and of y (as torch.minimum
+ * / torch.maximum: NaN once an operand is).  The item is skipped (hand_w = 1 everywhere) when either sum == 0 or either hand
+ * has no entry > 0.  Else per axis: centre = (min + max) / 2, width = max - min, lo = centre - (0.5f * width) * 1.2f,
+ * hi = centre + (0.5f * width) * 1.2f, w = hi - lo; x2 = w + lo (the reference's xywh -> xyxy); with (x1, y1, x2, y2) per hand:
+ *     inter = max(0, min(lx2, rx2) - max(lx1, rx1)) * max(0, min(ly2, ry2) - max(ly1, ry1))
+ *     area = (x2 - x1) * (y2 - y1);   iou = inter / (((area_l + area_r) - inter) + 1e-5f)
+ * If iou > 0.5f the hand with the larger depth loses (the right one on a tie): hand_w = 0 for the keypoints whose part[k] has
+ * that hand's bit (1 left, 2 right; the hand's rows and its wrist), 1 elsewhere.
+ *     loss = ((|proj - gt| * valid) * hand_w) * weight                     (the last product only with weight)
+ *     dL_dproj = (((g * weight) * hand_w) * valid) * sign(proj - gt),  sign(0) = 0
+ * B == 0 is a successful no-op in every call. */
+#define EXA_MESH_KPT_ROWS 256           /* threads per workgroup = vertices per partial of the g_mesh sum */
+#define EXA_MESH_KPT_BINS 79            /* rows of the dynamic landmark tables */
+#define EXA_MESH_KPT_JOINT 0
+#define EXA_MESH_KPT_VERTEX 1
+#define EXA_MESH_KPT_STATIC 2
+#define EXA_MESH_KPT_DYNAMIC 3
+
+/* The tables of one keypoint selection; every pointer is a device pointer. */
+typedef struct ExaMeshKeypoints {
+    int32_t V, J, K, Ld, C, T;           /* vertices, joints, keypoints, dynamic slots, chain length, touched vertices */
+    const int32_t* rec;                  /* [K + 1, 4] */
+    const float* rec_w;                  /* [K + 1, 3] */
+    const int32_t* dyn_vtx;              /* [79, Ld, 3] */
+    const float* dyn_w;                  /* [79, Ld, 3] */
+    const int32_t* chain;                /* [C] */
+    const int32_t* vrow;                 /* [V]: the vertex's row of voff, -1 when no record touches it */
+    const int32_t* voff;                 /* [T + 1] */
+    const int32_t* vent_k;               /* per entry: the record, */
+    const int32_t* vent_bin;             /* its bin (-1: static) */
+    const float* vent_w;                 /* and its weight */
+    const int32_t* joff;                 /* [J + 1] */
+    const int32_t* jent;                 /* the records naming each joint, ascending */
+} ExaMeshKeypoints;
+
+/* The partials per (b, c) of the g_mesh sum: ceil(V / 256); 0 for V <= 0. */
+int64_t exa_mesh_keypoints_blocks(int32_t V);
+
+/* Host only: the bytes of the backward's workspace (the rows [B, 2 K + 1, 3] and the partials [B, 3, blocks]). */
+int exa_mesh_keypoints_workspace_size(int32_t B, int32_t V, int32_t K, uint64_t* out_bytes);
+
+/* One launch, two with mesh_cam.  kpt_cam [B, K, 3], root_cam [B, 3], yaw_bin [B] int32: fully written; kpt_proj [B, K, 2]
+ * (NULL: not wanted; else focal and princpt are required) and mesh_cam [B, V, 3] (NULL: not wanted) likewise.  rot is
+ * required with Ld > 0 and unread otherwise. */
+int exa_mesh_keypoints_forward(const ExaMeshKeypoints* tables, int32_t B, const float* vertices, const float* joints,
+                               const float* rot, const float* trans, const float* focal, const float* princpt,
+                               int32_t root_rel, float* kpt_cam, float* root_cam, float* kpt_proj, float* mesh_cam,
+                               int32_t* yaw_bin, void* stream);
+
+/* Two launches, three with g_mesh_cam.  yaw_bin: the forward's.  workspace [dev]: exa_mesh_keypoints_workspace_size bytes,
+ * every section written before it is read.  d_vertices [B, V, 3] and d_joints [B, J, 3] fully written; d_trans [B, 3]
+ * written when trans is given (NULL: not wanted). */
+int exa_mesh_keypoints_backward(const ExaMeshKeypoints* tables, int32_t B, const float* vertices, const float* joints,
+                                const float* trans, const float* focal, const float* princpt, int32_t root_rel,
+                                const int32_t* yaw_bin, const float* g_kpt_cam, const float* g_kpt_proj,
+                                const float* g_root_cam, const float* g_mesh_cam, void* workspace, uint64_t workspace_bytes,
+                                float* d_vertices, float* d_joints, float* d_trans, void* stream);
+
+/* One launch, one wave per item.  lhand_idx [n_lhand], rhand_idx [n_rhand], part [K] int32 [dev]; hand_w [B, K] and loss
+ * [B, K, 2] fully written. */
+int exa_mesh_coord_loss_forward(int32_t B, int32_t K, int32_t n_lhand, int32_t n_rhand, const int32_t* lhand_idx,
+                                const int32_t* rhand_idx, const int32_t* part, const float* kpt_proj,
+                                const float* kpt_proj_gt, const float* kpt_valid, const float* kpt_cam, const float* weight,
+                                float* hand_w, float* loss, void* stream);
+
+/* One launch, one thread per element.  hand_w: the forward's; dL_dkpt_proj [B, K, 2] fully written. */
+int exa_mesh_coord_loss_backward(int32_t B, int32_t K, const float* kpt_proj, const float* kpt_proj_gt,
+                                 const float* kpt_valid, const float* weight, const float* hand_w, const float* grad_loss,
+                                 float* dL_dkpt_proj, void* stream);
 
 #ifdef __cplusplus
 }
